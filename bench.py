@@ -20,6 +20,16 @@ Warm-up has two parts: a clock warm-up that runs untimed steps until at least
 warm-up), then the --warmup steps the driver asks for.  The timed region is
 exactly --steps steps.
 
+A plain run does what the headline figure needs and no more: set up, warm up,
+time the steps, print the result line (`metric`, `value`, `unit`,
+`ms_per_step`, the configuration).  --dump-outputs DIR also writes what the
+last timed step computed (the parity and rebuilt rows of a fixed sample of
+groups) as DIR/<name>.npy; the inputs are seeded, so two builds can be
+compared output for output.  --full adds, after the timed steps, everything
+else: the kernel-timing pass (`roofline`, `kernels`), the full-size
+verification (`verify`), the measured ceilings, the strong-scaling, host-path,
+per-call and rx_tx legs and the CPU baseline.
+
 Multi-GPU: `python bench.py --gpus N` (N > 1, no torchrun environment) starts
 N rank processes itself -- a child `torch.distributed.run` on 127.0.0.1, before
 anything in this process touches a GPU -- and forwards rank 0's JSON line.
@@ -32,7 +42,7 @@ gloo on the host (--dist-backend): they are control, not data, so RCCL has
 nothing to carry.
 
 Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--groups G]
-                       [--total-groups T]
+                       [--total-groups T] [--full] [--dump-outputs DIR]
 """
 from __future__ import annotations
 
@@ -87,6 +97,14 @@ def parse(argv=None):
                          "ugo_fec_reconstruct_into (erased rows written to a separate [p][G][pitch] output batch, "
                          "the fresh buffers klauspost's Reconstruct gives ugo's nil shards)")
     ap.add_argument("--seed", type=int, default=0x5EED)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run everything else this benchmark measures or checks: the "
+                         "kernel-timing pass (`roofline`, `kernels`), the full-size verification, the ceilings, the "
+                         "strong, host-path, per-call and rx_tx legs and the CPU baseline (each with its own switch "
+                         "below). Without it a run sets up, warms up, times --steps steps and prints the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed to DIR/<name>.npy "
+                         "(float32): the parity rows and the rebuilt rows of a fixed, seeded sample of groups")
     ap.add_argument("--dist-backend", choices=["gloo", "nccl"], default="gloo",
                     help="process group for the timing barrier and reductions (no data-path collective)")
     ap.add_argument("--cpu-baseline-seconds", type=float, default=8.0,
@@ -1751,6 +1769,40 @@ def packet_decode_case(enc, dev, reps, kernel_ms, npk=851968):
             "verify_all_decode": ok}
 
 
+DUMP_ELEMS = 12_000_000  # float32 elements over all dumped arrays: 48 MB
+
+
+def dump_outputs(path, batch, out, planar, oplanar, d, p, S, seed, rank, world):
+    """--dump-outputs: what the last timed step left its caller, as float32
+    .npy files under `path`, for a sample of the batch's groups (all of them
+    if they fit in DUMP_ELEMS; else a fixed choice seeded by --seed, ascending):
+      parity.npy     [k][p][S]  the parity rows encode_batch wrote into the batch
+      recovered.npy  [k][p][S]  reconstruct_into's output rows of those groups (slot
+                                j = the j-th erased row; slots past the erasure
+                                count keep the output batch's initial zeros)
+    or, with --decode inplace (out is None), one array:
+      batch.npy      [k][d+p][S]  the batch after encode + in-place reconstruct
+    Ranks of an N > 1 run write <name>.rank<r>.npy, each for its own batch."""
+    import numpy as np
+    import torch
+
+    view = batch.transpose(0, 1) if planar else batch  # [G][d+p][pitch] either way
+    G = view.shape[0]
+    per_group = 2 * p * S if out is not None else (d + p) * S
+    k = max(1, min(G, DUMP_ELEMS // per_group))
+    idx = np.arange(G) if k == G else np.sort(np.random.default_rng(seed).choice(G, k, replace=False))
+    gi = torch.as_tensor(idx, device=batch.device)
+    if out is not None:
+        o = out.transpose(0, 1) if oplanar else out  # [G][p][out pitch]
+        arrays = {"parity": view[gi, d:, :S], "recovered": o[gi, :, :S]}
+    else:
+        arrays = {"batch": view[gi, :, :S]}
+    os.makedirs(path, exist_ok=True)
+    sfx = f".rank{rank}" if world > 1 else ""
+    for name, t in arrays.items():
+        np.save(os.path.join(path, name + sfx + ".npy"), t.cpu().numpy().astype(np.float32))
+
+
 def run_rank(args):
     import numpy as np
     import torch
@@ -1812,6 +1864,7 @@ def run_rank(args):
     sync = torch.cuda.synchronize
     cw_ms, cw_steps, cw_settled = clock_warmup(step, sync, args.clock_warmup_ms)
     barrier(world)  # ranks start the counted warm-up together, none idles after its clock warm-up
+    cur[0] = 0  # the clock warm-up's step count varies: the counted steps start at batch 0 in every run
     for _ in range(args.warmup):
         step()
     sync()
@@ -1819,6 +1872,53 @@ def run_rank(args):
     # 1. The timed region (`value`): K steps of ordinary launches, barrier +
     #    synchronize on both sides, max over ranks.
     elapsed = timed_region(step, args.steps, sync, world)
+    if args.dump_outputs:
+        last = (cur[0] - 1) % nb  # the batch the last timed step worked on
+        dump_outputs(args.dump_outputs, batches[last], outs[last] if into else None, planar, oplanar, d, p, S,
+                     args.seed, rank, world)
+
+    step_bytes_all = total_groups * (n * S + (d + e) * S)
+
+    def result_line(elapsed):
+        """The result line of a plain run: the timed region and its setup."""
+        value = step_bytes_all * args.steps / elapsed / 2**30
+        if scaling == "strong":
+            workload = f"{total_groups} groups total, strong: {G} groups on rank 0"
+        else:
+            workload = f"{G} groups/GPU, weak: {total_groups} groups total"
+        out = {
+            "metric": METRIC, "value": round(value, 3), "unit": "GiB/s", "n_gpus": world, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 4), "higher_is_better": True,
+            "scaling": scaling, "vs_baseline": None, "dtype": "u8",
+            "data": "synthetic: device-generated uniform random bytes (seeded), "
+                    f"{e} distinct uniformly random erased shards per group",
+            "config": {"workload": f"({d}+{p})x{S}B groups, encode + {e}-erasure reconstruct, device-resident, "
+                                   + workload, "groups_per_gpu": G, "total_groups": total_groups,
+                       "data_shards": d, "parity_shards": p, "shard_size": S, "pitch": pitch, "erasures": e,
+                       "layout": "shard-major [d+p][G][pitch]" if planar else "group-major [G][d+p][pitch]",
+                       "row_stride": (G * pitch + args.row_pad) if planar else pitch,
+                       "batches_per_gpu": nb, "decode": args.decode,
+                       "parallelism": f"dp{world} (independent packet groups, no collective)"},
+            "clock_warmup_ms": round(cw_ms, 1), "clock_warmup_steps": cw_steps, "clock_settled": cw_settled,
+            "untimed_steps_total": cw_steps + args.warmup,
+            "pct_hbm_roofline": round(step_bytes_all / world * args.steps / elapsed / (HBM_PEAK_GBS * 1e9), 4),
+        }
+        if ranks_per_device > 1:
+            out["config"]["ranks_per_device"] = ranks_per_device
+            out["note"] = (f"{world} ranks on {ndev} device(s): a launcher rehearsal, not an {world}-GPU "
+                           f"measurement")
+        return out
+
+    if not args.full:
+        # a plain run ends here: the headline figure needs nothing below
+        elapsed = reduce_max([elapsed], world)[0]
+        if rank == 0:
+            print(json.dumps(result_line(elapsed)), flush=True)
+        if world > 1:
+            import torch.distributed as dist
+
+            dist.destroy_process_group()
+        return
 
     # 2. Kernel-timing pass (`roofline`, `kernels`): the same K steps again with
     #    per-launch start/stop events (kernel_pass); the value pass above runs
@@ -1829,8 +1929,6 @@ def run_rank(args):
 
     enc_bytes = G * n * S            # per launch, this rank
     dec_bytes = G * (d + e) * S
-    step_bytes_all = total_groups * (n * S + (d + e) * S)
-    value = step_bytes_all * args.steps / elapsed / 2**30
 
     # bit-exactness at full size (outside the timed region): erase, reconstruct, compare
     verify = None
@@ -1944,32 +2042,8 @@ def run_rank(args):
                         f"events on the launch stream (ms_per_step of that pass: "
                         f"{elapsed_timing_pass / args.steps * 1e3:.4f})"
                         + (f"; {traffic_note}" if traffic_note else "")})
-        if scaling == "strong":
-            workload = f"{total_groups} groups total, strong: {G} groups on rank 0"
-        else:
-            workload = f"{G} groups/GPU, weak: {total_groups} groups total"
-        out = {
-            "metric": METRIC, "value": round(value, 3), "unit": "GiB/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 4), "higher_is_better": True,
-            "scaling": scaling, "vs_baseline": None, "dtype": "u8",
-            "data": "synthetic: device-generated uniform random bytes (seeded), "
-                    f"{e} distinct uniformly random erased shards per group",
-            "config": {"workload": f"({d}+{p})x{S}B groups, encode + {e}-erasure reconstruct, device-resident, "
-                                   + workload, "groups_per_gpu": G, "total_groups": total_groups,
-                       "data_shards": d, "parity_shards": p, "shard_size": S, "pitch": pitch, "erasures": e,
-                       "layout": "shard-major [d+p][G][pitch]" if planar else "group-major [G][d+p][pitch]",
-                       "row_stride": (G * pitch + args.row_pad) if planar else pitch,
-                       "batches_per_gpu": nb, "decode": args.decode,
-                       "parallelism": f"dp{world} (independent packet groups, no collective)"},
-            "clock_warmup_ms": round(cw_ms, 1), "clock_warmup_steps": cw_steps, "clock_settled": cw_settled,
-            "untimed_steps_total": cw_steps + args.warmup,
-            "pct_hbm_roofline": round(step_bytes_all / world * args.steps / elapsed / (HBM_PEAK_GBS * 1e9), 4),
-            "roofline": roof, "kernels": kern, "verify": verify,
-        }
-        if ranks_per_device > 1:
-            out["config"]["ranks_per_device"] = ranks_per_device
-            out["note"] = (f"{world} ranks on {ndev} device(s): a launcher rehearsal, not an {world}-GPU "
-                           f"measurement")
+        out = result_line(elapsed)
+        out.update({"roofline": roof, "kernels": kern, "verify": verify})
         if strong is not None:
             out["strong_c4"] = strong
         if host is not None:

@@ -46,6 +46,46 @@ def test_main_dispatch(monkeypatch):
     assert calls[-1] == ("rank", 2)
 
 
+def test_plain_run_is_the_default():
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "3"])
+    assert a.full is False and a.dump_outputs is None and a.steps == 7 and a.warmup == 3
+    a = bench.parse(["--full", "--dump-outputs", "somewhere"])
+    assert a.full is True and a.dump_outputs == "somewhere"
+
+
+@pytest.mark.parametrize("planar", [True, False])
+def test_dump_outputs_sample(tmp_path, planar, monkeypatch):
+    """--dump-outputs on host tensors: float32 arrays of the groups' parity and
+    output rows, whichever layout the batches have; a batch too large for the
+    budget is sampled, the same groups on every call."""
+    import numpy as np
+    import torch
+
+    d, p, S, pitch, G = 4, 2, 5, 16, 9
+    gen = torch.Generator().manual_seed(3)
+    gm = torch.randint(0, 256, (G, d + p, pitch), dtype=torch.uint8, generator=gen)  # group-major truth
+    om = torch.randint(0, 256, (G, p, pitch), dtype=torch.uint8, generator=gen)
+    batch = gm.transpose(0, 1).contiguous() if planar else gm
+    out = om.transpose(0, 1).contiguous() if planar else om
+    bench.dump_outputs(str(tmp_path / "a"), batch, out, planar, planar, d, p, S, 1, 0, 1)
+    par = np.load(tmp_path / "a" / "parity.npy")
+    rec = np.load(tmp_path / "a" / "recovered.npy")
+    assert par.dtype == np.float32 and rec.dtype == np.float32
+    assert np.array_equal(par, gm[:, d:, :S].numpy()) and np.array_equal(rec, om[:, :, :S].numpy())
+    # in place: the whole batch, one file per rank when there are several
+    bench.dump_outputs(str(tmp_path / "b"), batch, None, planar, planar, d, p, S, 1, 1, 2)
+    assert np.array_equal(np.load(tmp_path / "b" / "batch.rank1.npy"), gm[:, :, :S].numpy())
+    # 3 groups' worth of budget: a seeded, ascending choice of 3 groups
+    monkeypatch.setattr(bench, "DUMP_ELEMS", 3 * 2 * p * S)
+    for name in ("c", "d"):
+        bench.dump_outputs(str(tmp_path / name), batch, out, planar, planar, d, p, S, 1, 0, 1)
+    par = np.load(tmp_path / "c" / "parity.npy")
+    assert par.shape == (3, p, S) and np.array_equal(par, np.load(tmp_path / "d" / "parity.npy"))
+    idx = np.sort(np.random.default_rng(1).choice(G, 3, replace=False))
+    assert np.array_equal(par, gm[idx][:, d:, :S].numpy())
+    assert np.array_equal(np.load(tmp_path / "c" / "recovered.npy"), om[idx][:, :, :S].numpy())
+
+
 def test_result_line_filter():
     assert bench.is_result_line('{"metric": "x", "value": 1}\n')
     assert not bench.is_result_line('{"other": 1}')

@@ -15,7 +15,7 @@ for rep in $(seq 1 $REPS); do
       if [ -z "$rest" ] && [[ "$t" == *=* && "$t" != -* ]]; then envs="$envs $t"; else rest="$rest $t"; fi
     done
     f=$OUT/ab_${TAG}_${label}_$rep
-    timeout -k 10 180 env $envs python bench.py $rest --no-cpu-baseline --no-host-path --c4-total-groups 0 > $f.json 2> $f.err
+    timeout -k 10 180 env $envs python bench.py --full $rest --no-cpu-baseline --no-host-path --c4-total-groups 0 > $f.json 2> $f.err
     rc=$?; [ $rc -eq 0 ] || { echo "bench $label rc=$rc"; tail -5 $f.err; exit $rc; }
     python -c "import json,sys; d=json.load(open(sys.argv[1])); k=d['kernels']; print(sys.argv[2], d['value'], d['ms_per_step'], round(k['encode']['avg_ms']*1e3,1), k['encode']['frac'], round(k['reconstruct']['avg_ms']*1e3,1), k['reconstruct']['frac'], all(d['verify'].values()))" $f.json $label
   done

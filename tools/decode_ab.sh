@@ -8,9 +8,10 @@ OUT=gpurun_out/decode_ab.jsonl; : > $OUT
 timeout -k 10 600 python -u -m pytest tests -m gpu -x -q --timeout 120 --timeout-method thread \
   > gpurun_out/pytest_gpu_into.log 2>&1 || { echo "pytest rc=$?"; tail -30 gpurun_out/pytest_gpu_into.log; exit 1; }
 tail -3 gpurun_out/pytest_gpu_into.log
+DIR=$(dirname $OUT)
 for pass in 1 2; do
   for mode in inplace into; do
-    timeout -k 10 120 python bench.py --decode $mode --no-cpu-baseline > gpurun_out/dab.json 2> gpurun_out/dab.err \
+    timeout -k 10 120 python bench.py --full --decode $mode --no-cpu-baseline > $DIR/dab.json 2> $DIR/dab.err \
       || { echo "bench $mode rc=$?"; tail -5 gpurun_out/dab.err; exit 1; }
     python -c "
 import json; r=json.load(open('gpurun_out/dab.json')); k=r['kernels']

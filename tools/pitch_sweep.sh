@@ -8,7 +8,7 @@ OUT=gpurun_out/pitch_sweep.jsonl
 mkdir -p gpurun_out; : > $OUT
 for pass in 1 2; do
   for pitch in ${PITCHES:-1360 1408 1472 1536}; do
-    timeout -k 10 120 python bench.py --pitch $pitch --no-cpu-baseline --steps 200 --warmup 50 \
+    timeout -k 10 120 python bench.py --full --pitch $pitch --no-cpu-baseline --steps 200 --warmup 50 \
       > gpurun_out/ps.json 2> gpurun_out/ps.err || { echo "pitch $pitch rc=$?"; tail -5 gpurun_out/ps.err; exit 1; }
     python - "$pitch" "$pass" >> $OUT <<'PY'
 import json, sys

@@ -11,7 +11,7 @@ for v in "$@"; do
   label=${v%%|*}; args=${v#*|}
   for ctr in FETCH_SIZE WRITE_SIZE; do
     timeout -s KILL 120 rocprofv3 --pmc $ctr --output-format csv -d "$OUT/${label}_$ctr" -o run -- python3 bench.py \
-      --steps 20 --warmup 20 --no-verify --no-cpu-baseline --no-host-path --c4-total-groups 0 $args \
+      --full --steps 20 --warmup 20 --no-verify --no-cpu-baseline --no-host-path --c4-total-groups 0 $args \
       > "$OUT/${label}_$ctr.json" 2> "$OUT/${label}_$ctr.err"
     rc=$?; [ $rc -eq 0 ] || { echo "$label $ctr rc=$rc"; tail -3 "$OUT/${label}_$ctr.err"; exit $rc; }
     python3 - "$OUT/${label}_$ctr" "$label" "$ctr" <<'PY'

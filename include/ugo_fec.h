@@ -60,7 +60,10 @@ extern "C" {
 /* 9: ugo_fec_rx_assemble_frames (frame rows: each placed row holds its
  *    decrypted packet, payload at column 6); the low-priority host copy queue is
  *    on by default, and the service pool holds at most 3 queues (8 hardware
- *    queues per process, see ugo_fec_set_host_copy_queue). */
+ *    queues per process, see ugo_fec_set_host_copy_queue).
+ *    Added without a version change (new symbols and values only):
+ *    ugo_fec_packet_encode with ugo_pkt_status 7-9 (ugo_pkt.h) and
+ *    UGO_FEC_KERNEL_PACKET_ENCODE. */
 #define UGO_FEC_ABI_VERSION 9
 
 /* Status codes.  1..5 map 1:1 onto the klauspost/reedsolomon error values
@@ -459,6 +462,7 @@ int ugo_fec_rc4_keystream(const uint8_t* key, size_t key_len, uint8_t* out, size
 #define UGO_FEC_KERNEL_RX 5          /* ugo_fec_rx_assemble                     */
 #define UGO_FEC_KERNEL_TX 6          /* ugo_fec_tx_assemble                     */
 #define UGO_FEC_KERNEL_PACKET 7      /* ugo_fec_packet_decode                   */
+#define UGO_FEC_KERNEL_PACKET_ENCODE 8 /* ugo_fec_packet_encode                 */
 
 typedef struct ugo_fec_launch_time {
   uint32_t kernel; /* UGO_FEC_KERNEL_* */

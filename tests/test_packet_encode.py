@@ -1,0 +1,453 @@
+"""ugo packet wire codec, TX half: the batch encoder
+(ugo_fec_packet_encode, k_packet_encode) against the restated ugoPacket.encode /
+sack.write / segment.write / WriteUfloat16 / PutUvarint (oracle/packet_ref.py,
+checker only), byte for byte.
+
+Every packet is described as the encoder's input (info / ranges / segs over a
+payload buffer) and as the oracle's arguments; the expected bytes are the
+oracle's, except where a comment beside the case derives them by hand (slot
+capacity, which the oracle does not know, and a gap of 2^40).  The oracle's
+write_sack does not restate the two consistency checks of packet.go:367-372,
+so _ref_encode restates them in front of it.  Every slot is pre-filled with a
+sentinel: the encoder may write bytes [0, round_up(len, 16)) of a slot and
+nothing else.
+"""
+import numpy as np
+import pytest
+import torch
+
+import packet_ref as pr
+from ugo_amd import fec
+
+KEY = b"1234567890123456"  # ugo/listener.go:92, ugo/dial.go:132
+SENTINEL = 0xA5
+M64 = (1 << 64) - 1
+
+
+def _pkt(flags=0, sack=None, pn=1, sw=0, segments=()):
+    """sack = (largest, in_order, ranges, delay_us) or None; segments = [(offset, data)]."""
+    return {"flags": flags, "sack": sack, "pn": pn, "sw": sw, "segments": list(segments)}
+
+
+def _ref_encode(p):
+    """(status, bytes) of ugoPacket.encode: the oracle behind the reference's
+    two consistency checks (packet.go:367-372)."""
+    s = p["sack"]
+    if s is not None and s[2]:
+        if s[2][0][1] != s[0]:
+            return fec.PKT_INCONSISTENT_LARGEST_ACKED, b""
+        if s[1] != s[2][-1][0]:
+            return fec.PKT_INCONSISTENT_LOWEST_ACKED, b""
+    try:
+        return 0, pr.encode(flags=p["flags"], sack=s, packet_number=p["pn"], stop_waiting=p["sw"],
+                            segments=p["segments"])
+    except pr.EncodeError:
+        return fec.PKT_INCONSISTENT_RANGE_COUNT, b""
+
+
+def _two_ranges(gap, hi=1 << 20):
+    """A SACK of two ranges with `gap` missing packets between them."""
+    lo_last = hi - 10 - gap - 1
+    ranges = [(hi - 10, hi), (lo_last - 4, lo_last)]
+    return (hi, ranges[-1][0], ranges, 7)
+
+
+# ------------------------------------------------------------------ CPU tests
+def test_null_context_is_invalid_arg():
+    assert fec.load_library().ugo_fec_packet_encode(None, None, None, 0, None, 0, None, 0, 0, None, 0, None, 0,
+                                                    None, None, None) == 6
+
+
+def test_status_names_and_symbol():
+    assert (fec.PKT_INCONSISTENT_LARGEST_ACKED, fec.PKT_INCONSISTENT_LOWEST_ACKED,
+            fec.PKT_INCONSISTENT_RANGE_COUNT) == (7, 8, 9)
+    hdr = open(fec.PKT_HEADER_PATH).read()
+    for name, val in [("UGO_PKT_INCONSISTENT_LARGEST_ACKED", 7), ("UGO_PKT_INCONSISTENT_LOWEST_ACKED", 8),
+                      ("UGO_PKT_INCONSISTENT_RANGE_COUNT", 9)]:
+        assert f"{name} = {val}" in hdr
+    assert "ugo_fec_packet_encode" in fec.header_symbols()
+    assert fec.KERNEL_NAMES[8] == "packet_encode" and fec.KERNEL_IDS["packet_encode"] == 8
+    assert "#define UGO_FEC_KERNEL_PACKET_ENCODE 8" in open(fec.HEADER_PATH).read()
+    assert fec.load_library().ugo_fec_abi_version() == 9
+
+
+def test_oracle_long_gap_pins():
+    """numWritableNackRanges counts ceil((gap+1)/256) blocks, the writer emits
+    ceil(gap/255): exactly these gaps below 1600 disagree."""
+    bad = {511, 766, 767, *range(1021, 1024), *range(1276, 1280), *range(1531, 1536)}
+    for gap in range(1, 1600):
+        st, raw = _ref_encode(_pkt(sack=_two_ranges(gap)))
+        assert (st == 9) == (gap in bad), gap
+    for gap in (510, 512, 765, 768):
+        assert _ref_encode(_pkt(sack=_two_ranges(gap)))[0] == 0
+
+
+def _many_ranges(n, hi=1 << 20):
+    ranges = []
+    for _ in range(n):  # length 3, gap 3
+        ranges.append((hi - 2, hi))
+        hi -= 6
+    return (ranges[0][1], ranges[-1][0], ranges, 0)
+
+
+def test_oracle_truncation_gap0_and_single_range_pins():
+    s = _many_ranges(300)
+    st, raw = _ref_encode(_pkt(sack=s, pn=1))
+    assert st == 0 and len(raw) == 517
+    dst, out = pr.decode(raw)
+    assert dst == 0 and out["sack"]["ranges"] == s[2][:255]  # the writer stops at 255 blocks, no error
+    adjacent = [(100, 110), (90, 99)]  # gap 0: no block is written for the second range
+    assert _ref_encode(_pkt(sack=(110, 90, adjacent, 0)))[0] == 9
+    st, raw = _ref_encode(_pkt(sack=(110, 100, [(100, 110)], 0)))
+    assert st == 0 and pr.decode(raw)[0] == pr.PKT_INVALID_ACK_RANGES  # block count byte 0
+
+
+# ------------------------------------------------------------ GPU batch tools
+def _describe(pkts, rng, max_ranges, max_segments, residues=None):
+    """The encoder's input for `pkts`: info / ranges / segs arrays and one flat
+    payload buffer holding every segment's bytes at a random (or the given)
+    residue mod 16, with unrelated bytes around them."""
+    n = len(pkts)
+    info = np.zeros(n, fec.PKT_INFO_DTYPE)
+    ranges = np.zeros((n, max_ranges, 2), np.uint64)
+    segs = np.zeros((n, max_segments), fec.PKT_SEGMENT_DTYPE)
+    blob = bytearray(rng.integers(0, 256, 16, dtype=np.uint8).tobytes())
+    for i, p in enumerate(pkts):
+        I = info[i]
+        I["flags"] = p["flags"] | (0x80 if p["sack"] is not None else 0)
+        I["packet_number"], I["stop_waiting"] = p["pn"], p["sw"]
+        I["status"], I["payload_off"], I["fec_flag_lo"] = 0xDEAD, 0xBEEF, 0x5A  # ignored by the encoder
+        if p["sack"] is not None:
+            I["largest_acked"], I["largest_in_order"], rg, I["delay_us"] = p["sack"]
+            I["n_ranges"] = len(rg)
+            for k, (f, l) in enumerate(rg[:max_ranges]):
+                ranges[i, k] = (f & M64, l & M64)
+        I["n_segments"] = len(p["segments"])
+        for j, (off, data) in enumerate(p["segments"][:max_segments]):
+            want = int(rng.integers(0, 16)) if residues is None else residues[i]
+            blob += bytes((want - len(blob)) % 16)
+            segs[i, j] = (off, len(blob), len(data), 0xFFFF)  # avail is ignored
+            blob += data
+            blob += rng.integers(0, 256, int(rng.integers(0, 5)), dtype=np.uint8).tobytes()
+    blob += bytes(16)
+    return info, ranges, segs, np.frombuffer(bytes(blob), np.uint8)
+
+
+def _encode(enc, info, ranges, segs, payload, slot, payload_stride=0, framed=False, pad=None):
+    """Runs the encoder over sentinel-filled slots (one guard slot behind the
+    last) and checks that nothing outside [0, round_up(len, 16)) was written."""
+    n = len(info)
+    buf = torch.full((n + 1, slot), SENTINEL, dtype=torch.uint8, device="cuda")
+    lens = torch.full((n,), -1, dtype=torch.int16, device="cuda")
+    status = torch.full((n,), 0xEE, dtype=torch.uint8, device="cuda")
+    d_info = torch.from_numpy(info.view(np.uint8).reshape(n, 64).copy()).cuda()
+    d_ranges = torch.from_numpy(ranges.view(np.int64)).cuda()
+    d_segs = torch.from_numpy(segs.view(np.uint8).reshape(n, -1, 16).copy()).cuda()
+    d_pay = payload if torch.is_tensor(payload) else torch.from_numpy(payload.copy()).cuda()
+    enc.packet_encode(d_info, d_ranges, d_segs, d_pay, slot, payload_stride=payload_stride, pad=pad, framed=framed,
+                      out=(buf[:n], lens, status))
+    torch.cuda.synchronize()
+    wire, wl, st = buf.cpu().numpy(), lens.cpu().numpy().view(np.uint16), status.cpu().numpy()
+    assert (wire[n] == SENTINEL).all(), "guard slot written"
+    for i in range(n):
+        assert (wire[i, (int(wl[i]) + 15) & ~15:] == SENTINEL).all(), (i, "bytes past round_up(len, 16) written")
+    return wire[:n], wl, st
+
+
+def _check(expected, wire, wl, st, framed=False, ks=None):
+    room = 6 if framed else 0
+    for i, (est, raw) in enumerate(expected):
+        assert st[i] == est, f"packet {i}: status {st[i]} vs {est}"
+        if est != 0:
+            assert wl[i] == 0 and (wire[i] == SENTINEL).all(), (i, "a failed packet's slot was touched")
+            continue
+        want = np.frombuffer(bytes(room) + raw, np.uint8)
+        assert wl[i] == len(want), (i, wl[i], len(want))
+        if ks is not None:
+            want = want ^ ks[:len(want)]
+        got = wire[i, :len(want)]
+        assert (got == want).all(), f"packet {i}: first difference at byte {int(np.argmax(got != want))}"
+        assert (wire[i, len(want):(len(want) + 15) & ~15] == 0).all(), (i, "padding up to the chunk is not zero")
+
+
+def _random_desc(rng):
+    """tests/test_packet_codec.py's _random_packet, as a description; packets the
+    reference fails to encode stay in (status 9)."""
+    kind = rng.integers(0, 6)
+    sack = None
+    if kind in (0, 2, 3, 5):
+        largest = int(rng.integers(1, 1 << int(rng.integers(1, 40))))
+        if kind in (3, 5):
+            ranges, hi = [], largest
+            for _ in range(int(rng.integers(2, 7))):
+                lo = hi - int(rng.integers(0, 20))
+                if lo < 1:
+                    break
+                ranges.append((lo, hi))
+                hi = lo - 2 - int(rng.integers(0, 600 if kind == 5 else 200))
+                if hi < 1:
+                    break
+            if len(ranges) < 2:
+                ranges = []
+            in_order = ranges[-1][0] if ranges else max(1, largest - int(rng.integers(0, 50)))
+            sack = (largest, in_order, ranges, int(rng.integers(0, 1 << 30)))
+        else:
+            sack = (largest, max(1, largest - int(rng.integers(0, 50))), [], int(rng.integers(0, 5000)))
+    segs = []
+    if kind != 2:
+        for _ in range(int(rng.integers(1, 4)) if kind == 4 else 1):
+            segs.append((int(rng.integers(0, 1 << int(rng.integers(1, 60)))),
+                         rng.integers(0, 256, int(rng.integers(0, 400)), dtype=np.uint8).tobytes()))
+    stop = int(rng.integers(1, 1 << 20)) if rng.random() < 0.3 else 0
+    pn = int(rng.integers(1, 1 << int(rng.integers(1, 62))))
+    flags = int(rng.choice([0, pr.finFlag, pr.rstFlag])) if rng.random() < 0.2 else 0
+    return _pkt(flags, sack, pn, stop, segs)
+
+
+def _data(rng, n):
+    return rng.integers(0, 256, n, dtype=np.uint8).tobytes()
+
+
+def _corpus(seed, n=600):
+    rng = np.random.default_rng(seed)
+    pk = [_random_desc(rng) for _ in range(n)]
+    ack = (1000, 990, [], 7)
+    pk += [_pkt(sack=ack, pn=5),                       # pure ACK: flags == 0x80, no packet number
+           _pkt(sack=_two_ranges(300), pn=5),          # pure ACK with ranges and a long gap
+           _pkt(pr.finFlag, None, 9), _pkt(pr.finFlag, ack, 9), _pkt(pr.rstFlag, None, 9), _pkt(pr.rstFlag, ack, 9),
+           _pkt(pn=3, sw=0, segments=[(0, _data(rng, 40))]), _pkt(pn=3, sw=77777, segments=[(0, _data(rng, 40))]),
+           _pkt(sack=ack, pn=3, sw=1),
+           _pkt(sack=_two_ranges(255), pn=4), _pkt(sack=_two_ranges(1020), pn=4),  # gaps that are multiples of 255
+           _pkt(sack=_two_ranges(767), pn=4, segments=[(9, _data(rng, 30))]),     # the reference fails: status 9
+           _pkt(sack=(110, 90, [(100, 110), (90, 99)], 0), pn=4),                   # adjacent ranges: status 9
+           _pkt(sack=(110, 100, [(100, 110)], 0), pn=4)]                            # a single range
+    pk += [_pkt(pn=7, segments=[(1 << 14, _data(rng, L))]) for L in (0, 1, 15, 16, 17, 1400)]
+    pk += [_pkt(pn=7, sack=ack, sw=3, segments=[(1, _data(rng, 33)), (1 << 33, _data(rng, 0)), (5, _data(rng, 160))])]
+    pk += [_pkt(pn=v, segments=[(w, _data(rng, 50))]) for v in (1 << 63, M64) for w in (1 << 63, M64)]  # 10-B varints
+    pk += [_pkt(sack=(1000, 990, [], d), pn=2) for d in (0, 4095, 4096, 1 << 30, 1 << 50)]  # 2^50 clamps to 0xFFFF
+    return pk
+
+
+# ------------------------------------------------------------------ GPU tests
+@pytest.mark.gpu
+def test_packet_encode_corpus_vs_oracle(gpu):
+    enc = fec.New(10, 3)
+    rng = np.random.default_rng(100)
+    pk = _corpus(1)
+    expected = [_ref_encode(p) for p in pk]
+    assert {0, 9} <= {st for st, _ in expected}
+    assert pr.write_ufloat16(1 << 50) == b"\xff\xff"
+    slot = max(len(raw) for _, raw in expected) + 15 & ~15
+    info, ranges, segs, payload = _describe(pk, rng, 8, 3)
+    wire, wl, st = _encode(enc, info, ranges, segs, payload, slot)
+    _check(expected, wire, wl, st)
+
+
+# (packet-number bytes, offset bytes): the segment data starts at byte
+# 1 + a + b + 2 of the packet -- 5 ... 20, every residue mod 16
+_ALIGN = [(a, s - a) for s in range(2, 18) for a in [min(10, s - 1)]]
+
+
+def _alignment_packets(rng):
+    pk, res = [], []
+    for rnd in range(2):  # 2 x 16 x 16 = 512 packets; the second round with another length and a stop-waiting
+        for a, b in _ALIGN:
+            for r in range(16):
+                pn, off = 1 << (7 * (a - 1)), 1 << (7 * (b - 1))
+                pk.append(_pkt(pn=pn, sw=0 if rnd == 0 else 300, segments=[(off, _data(rng, 100 + 7 * rnd))]))
+                res.append(r)
+    return pk, res
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("framed", [False, True])
+def test_packet_encode_alignment_sweep(gpu, framed):
+    enc = fec.New(10, 3)
+    rng = np.random.default_rng(7)
+    pk, res = _alignment_packets(rng)
+    expected = [_ref_encode(p) for p in pk]
+    starts = {len(raw) - 100 for _, raw in expected[:256]}
+    assert {s % 16 for s in starts} == set(range(16)) and all(st == 0 for st, _ in expected)
+    for n in (512, 1, 2, 3, 257):
+        info, ranges, segs, payload = _describe(pk[:n], rng, 1, 1, residues=res)
+        assert [int(x) % 16 for x in segs[:, 0]["data_off"]] == res[:n]
+        wire, wl, st = _encode(enc, info, ranges, segs, payload, 160, framed=framed)
+        _check(expected[:n], wire, wl, st, framed=framed)
+
+
+@pytest.mark.gpu
+def test_packet_encode_status_paths(gpu):
+    enc = fec.New(10, 3)
+    rng = np.random.default_rng(9)
+    slot, max_ranges, max_segments = 544, 300, 2
+    hdr = 1 + 1 + 1 + 2  # flags, packet number, offset, length: an unframed packet of slot bytes holds slot - 5
+    s7 = _two_ranges(20)
+    s7 = (s7[0] + 1, s7[1], s7[2], s7[3])  # largest_acked != ranges[0].last
+    s8 = _two_ranges(20)
+    s8 = (s8[0], s8[1] - 1, s8[2], s8[3])  # largest_in_order != ranges[-1].first
+    ORACLE = object()
+    cases = [  # (packet, the status the issue states, where the expectation comes from, info patch)
+        (_pkt(sack=_two_ranges(511), pn=1), 9, ORACLE, None),
+        (_pkt(sack=_two_ranges(767), pn=1), 9, ORACLE, None),
+        (_pkt(sack=_two_ranges(510), pn=1), 0, ORACLE, None),
+        (_pkt(sack=_two_ranges(768), pn=1), 0, ORACLE, None),
+        # gap 2^40, by hand (the oracle's writer would loop 2^40 / 255 times): numWritableNackRanges stops at
+        # this range -- its 2^32 + 1 blocks do not stay below 255 -- and returns 1, the first block; the
+        # writer emits 2^40 / 255 + 1 blocks for it -> "inconsistent number of ACK ranges written"
+        (_pkt(sack=_two_ranges(1 << 40, hi=1 << 41), pn=1), 9, "hand", None),
+        (_pkt(sack=s7, pn=1), 7, ORACLE, None),
+        (_pkt(sack=s8, pn=1), 8, ORACLE, None),
+        (_pkt(sack=_many_ranges(300), pn=1), 0, ORACLE, None),  # truncated to 255 blocks, 517 bytes
+        (_pkt(pn=1, segments=[(1, _data(rng, slot - hdr))]), 0, ORACLE, None),  # exactly slot bytes
+        # by hand: slot + 1 bytes, n_ranges = max_ranges + 1, n_segments = max_segments + 1 -> UGO_PKT_CAPACITY
+        (_pkt(pn=1, segments=[(1, _data(rng, slot - hdr + 1))]), 6, "hand", None),
+        (_pkt(sack=_two_ranges(20), pn=1), 6, "hand", ("n_ranges", max_ranges + 1)),
+        (_pkt(pn=1, segments=[(1, _data(rng, 20)), (2, _data(rng, 20))]), 6, "hand", ("n_segments", max_segments + 1)),
+    ]
+    good = lambda: _pkt(pn=11, sw=4, segments=[(5, _data(rng, 90))])  # noqa: E731
+    pk, expected = [good()], []
+    expected.append(_ref_encode(pk[0]))
+    for p, want, source, _ in cases:  # every case between two good neighbours
+        st, raw = _ref_encode(p) if source is ORACLE else (want, b"")
+        assert st == want, (want, st)
+        pk += [p, good()]
+        expected += [(st, raw), _ref_encode(pk[-1])]
+    assert len(expected[2 * 7 + 1][1]) == 517 and len(expected[2 * 8 + 1][1]) == slot
+    info, ranges, segs, payload = _describe(pk, rng, max_ranges, max_segments)
+    for k, (_, _, _, patch) in enumerate(cases):
+        if patch is not None:
+            info[2 * k + 1][patch[0]] = patch[1]
+    wire, wl, st = _encode(enc, info, ranges, segs, payload, slot)
+    _check(expected, wire, wl, st)
+
+
+@pytest.mark.gpu
+def test_packet_encode_rc4_pad(gpu):
+    enc = fec.New(10, 3)
+    rng = np.random.default_rng(13)
+    pk = _corpus(2, n=150)
+    expected = [_ref_encode(p) for p in pk]
+    slot = max(len(raw) for _, raw in expected) + 15 & ~15
+    ks = np.frombuffer(fec.rc4_keystream(KEY, slot), np.uint8)
+    pad = torch.from_numpy(ks.copy()).cuda()
+    info, ranges, segs, payload = _describe(pk, rng, 8, 3)
+    wire, wl, st = _encode(enc, info, ranges, segs, payload, slot, pad=pad)
+    _check(expected, wire, wl, st, ks=ks)
+    # framed packets are encrypted by tx_assemble, after markData: a pad is refused
+    with pytest.raises(ValueError):
+        _encode(enc, info, ranges, segs, payload, slot, pad=pad, framed=True)
+    n = len(pk)
+    d = [torch.zeros(n * 64, dtype=torch.uint8, device="cuda") for _ in range(4)]
+    code = fec.load_library().ugo_fec_packet_encode(
+        enc._h, d[0].data_ptr(), None, 0, None, 0, None, 0, 1, pad.data_ptr(), fec.PKT_FEC_FRAMED, d[1].data_ptr(),
+        64, d[2].data_ptr(), d[3].data_ptr(), None)
+    assert code == fec.ErrInvalidArg.code
+
+
+def _round_trips(p, st):
+    """Where decode(encode(x)) == x in the reference: encodes, no gap that is
+    a multiple of 255 (written lossily, test_packet_codec.py), not a single range."""
+    if st != 0:
+        return False
+    rg = p["sack"][2] if p["sack"] else []
+    gaps = [rg[i - 1][0] - rg[i][1] - 1 for i in range(1, len(rg))]
+    return len(rg) != 1 and not any(g >= 255 and g % 255 == 0 for g in gaps)
+
+
+@pytest.mark.gpu
+def test_packet_encode_round_trip_through_decoder(gpu):
+    enc = fec.New(10, 3)
+    rng = np.random.default_rng(17)
+    pk = _corpus(3, n=300)
+    expected = [_ref_encode(p) for p in pk]
+    slot = max(len(raw) for _, raw in expected) + 15 & ~15
+    info, ranges, segs, payload = _describe(pk, rng, 8, 3)
+    wire, wl, st = _encode(enc, info, ranges, segs, payload, slot)
+    _check(expected, wire, wl, st)
+    d_wire = torch.from_numpy(wire.copy()).cuda()
+    d_len = torch.from_numpy(wl.view(np.int16).copy()).cuda()
+    dinfo, dranges, dsegs = enc.packet_decode(d_wire, d_len, max_ranges=8, max_segments=3)
+    torch.cuda.synchronize()
+    I = dinfo.cpu().numpy().view(fec.PKT_INFO_DTYPE).reshape(-1)
+    R = dranges.cpu().numpy().view(np.uint64)
+    S = dsegs.cpu().numpy().reshape(len(pk), -1).view(fec.PKT_SEGMENT_DTYPE).reshape(len(pk), -1)
+    keep = [i for i, p in enumerate(pk) if _round_trips(p, expected[i][0])]
+    assert len(keep) > 200
+    for i in keep:
+        p, raw = pk[i], expected[i][1]
+        assert I[i]["status"] == 0 and I[i]["flags"] == raw[0], i
+        assert I[i]["packet_number"] == (p["pn"] if raw[0] != 0x80 else 0) and I[i]["stop_waiting"] == p["sw"], i
+        if p["sack"] is not None:
+            largest, in_order, rg, delay = p["sack"]
+            assert (I[i]["largest_acked"], I[i]["largest_in_order"]) == (largest, in_order), i
+            assert I[i]["delay_us"] == pr.Reader(pr.write_ufloat16(delay)).read_ufloat16(), i
+            assert I[i]["n_ranges"] == len(rg) and [tuple(int(v) for v in x) for x in R[i, :len(rg)]] == rg, i
+        assert I[i]["n_segments"] == len(p["segments"]), i
+        for j, (off, data) in enumerate(p["segments"]):
+            s = S[i, j]
+            assert (s["offset"], s["len"], s["avail"]) == (off, len(data), len(data)), (i, j)
+            assert wire[i, s["data_off"]:s["data_off"] + s["len"]].tobytes() == data, (i, j)
+    # re-encode what the decoder produced: its segment views address the decoded packets themselves
+    sel = np.array(keep)
+    n = len(sel)
+    back, bl, bs = _encode(enc, I[sel], R[sel], S[sel], d_wire[torch.from_numpy(sel).cuda()].contiguous(), slot,
+                           payload_stride=slot)
+    _check([expected[i] for i in keep], back, bl, bs)
+    assert n == len(bl)
+
+
+@pytest.mark.gpu
+def test_packet_encode_feeds_tx_assemble(gpu):
+    d, p, slot = 10, 3, 1488
+    enc = fec.New(d, p)
+    rng = np.random.default_rng(19)
+    G = 8
+    pk = [_pkt(pn=1000 + i, sw=5 if i % 7 == 0 else 0, sack=(900 + i, 890, [], 12) if i % 4 == 0 else None,
+               segments=[(1400 * i, _data(rng, int(rng.integers(1, 1401))))]) for i in range(G * d)]
+    expected = [_ref_encode(q) for q in pk]
+    info, ranges, segs, payload = _describe(pk, rng, 1, 1)
+    wire, wl, st = _encode(enc, info, ranges, segs, payload, slot, framed=True)
+    _check(expected, wire, wl, st, framed=True)
+    host = np.zeros((G * d, slot), np.uint8)  # the same slots built on the host: 6 zero bytes, then the packet
+    for i, (_, raw) in enumerate(expected):
+        host[i, 6:6 + len(raw)] = np.frombuffer(raw, np.uint8)
+    mine = wire.copy()
+    for i in range(G * d):  # tx_assemble is given the encoder's slots as they are, sentinel tails included
+        assert (mine[i, :wl[i]] == host[i, :wl[i]]).all()
+    pad = torch.frombuffer(bytearray(fec.rc4_keystream(KEY, slot)), dtype=torch.uint8).cuda()
+    outs = []
+    for src in (mine, host):
+        w = torch.zeros((G * (d + p), slot), dtype=torch.uint8, device="cuda")
+        wlen = torch.zeros(G * (d + p), dtype=torch.int16, device="cuda")
+        status = torch.full((G,), -1, dtype=torch.int8, device="cuda")
+        enc.tx_assemble(torch.from_numpy(src).cuda(), torch.from_numpy(wl.view(np.int16).copy()).cuda(), w, wlen,
+                        first_seq=130, pad=pad, status=status)
+        torch.cuda.synchronize()
+        outs.append((w.cpu().numpy(), wlen.cpu().numpy(), status.cpu().numpy()))
+    assert (outs[0][2] == 0).all()
+    for a, b in zip(outs[0], outs[1]):
+        assert (a == b).all()
+
+
+@pytest.mark.gpu
+def test_packet_encode_out_of_domain_inputs_stay_in_their_slot(gpu):
+    """Inputs the reference never builds: whatever they encode to, the call
+    returns, every status is a ugo_pkt_status and no byte outside
+    [0, round_up(len, 16)) of a slot is written (checked by _encode)."""
+    enc = fec.New(10, 3)
+    rng = np.random.default_rng(23)
+    pk = [_pkt(pn=1, sack=_two_ranges(20), segments=[(3, _data(rng, 60))]) for _ in range(96)]
+    info, ranges, segs, payload = _describe(pk, rng, 4, 2)
+    for i in range(len(pk)):
+        kind = i % 3
+        if kind == 0:  # first > last
+            ranges[i, i % 2] = ranges[i, i % 2][::-1].copy()
+        elif kind == 1:
+            info[i]["largest_acked"] = 0
+        else:  # random info bytes, counts within the caps
+            raw = rng.integers(0, 256, 64, dtype=np.uint8)
+            info[i:i + 1].view(np.uint8)[:] = raw
+            info[i]["n_ranges"] = int(rng.integers(0, 5))
+            info[i]["n_segments"] = int(rng.integers(0, 2))
+    wire, wl, st = _encode(enc, info, ranges, segs, payload, 128)
+    assert ((st >= 0) & (st <= 9)).all()

@@ -25,6 +25,7 @@ enum KernelId : uint32_t {
   kKRx = 5,           // RX group assembly
   kKTx = 6,           // TX group assembly
   kKPacket = 7,       // packet wire decode
+  kKPacketEncode = 8, // packet wire encode
 };
 
 struct LaunchTimer {

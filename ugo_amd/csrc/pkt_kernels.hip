@@ -1,5 +1,7 @@
-// pkt_kernels.hip -- batch decoder for ugo's packet wire format on gfx950
-// (SURVEY.md §8f row 4).  One thread per packet restates, for a whole batch:
+// pkt_kernels.hip -- batch decoder and encoder for ugo's packet wire format on
+// gfx950.  The encoder (k_packet_encode) is described
+// where it starts, below.  Decoder: one thread per packet restates, for a
+// whole batch:
 //   Conn.handlePacket  ugo/conn.go:387-419  decrypt, strip the FEC header of
 //                                           typeData packets, ugoPacket.decode
 //   ugoPacket.decode   ugo/packet.go:138-177
@@ -229,12 +231,330 @@ __global__ __launch_bounds__(256) void k_packet_decode(PktArgs a) {
   a.info[i] = o;
 }
 
+// ---------------------------------------------------------------- encoder
+// Batch ugoPacket.encode (+ crypt.Encrypt as an XOR with `pad`):
+//   ugoPacket.encode       ugo/packet.go:182-228
+//   sack.write             ugo/packet.go:338-430
+//   numWritableNackRanges  ugo/packet.go:479-505
+//   segment.write          ugo/packet.go:101-110
+//   WriteUfloat16          ugo/utils/float16.go:54-86, binary.PutUvarint (Go stdlib)
+//
+// A block of 256 threads encodes kEncPacketsPerBlock packets in two phases.
+//   A. One thread per packet (the serial part, as in the decoder): it sizes the
+//      packet arithmetically (field sizes, status, total length; no byte is
+//      written before the packet is known to be valid and to fit), then writes
+//      every 16-B chunk that holds a header byte, a segment boundary or the
+//      packet's end through a 16-byte register window -- one aligned store per
+//      chunk.  The at most 15 segment bytes on either side of a segment's
+//      interior come out of two unaligned 16-B loads (the segment's first and
+//      last 16 bytes), not byte loads.  Whole chunks of segment data are
+//      skipped.
+//   B. kEncLanes lanes per packet copy those skipped interior chunks: one
+//      unaligned 16-B load from the payload, the pad XOR, one aligned 16-B
+//      store.  A segment's place in the packet follows from the position of
+//      the first segment header (left in LDS by phase A) and the sizes of the
+//      offset varints, so the lanes re-read only the segment descriptors.
+// Every chunk of [0, round_up(len, 16)) is stored exactly once, by one phase.
+//
+// Measured (tools/pkt_encode_probe.py, 851,968 packets with one 1400-B
+// segment, slot 1488; DESIGN.md §4.3, profiles/pkt_encode/): 0.53-0.56 ms
+// FEC-framed, 0.55-0.60 ms unframed with the pad, against 0.36 ms for an nt
+// copy of the same bytes.  Phase A alone takes 0.11 ms of it.  Nontemporal
+// stores in phase B: 0.64 -> 0.56 ms (nontemporal payload loads on top: no
+// change).  A wave instead of a half-wave per packet, 32 / 128 / 256 packets
+// per block instead of 64, and taking packets two at a time with both
+// packets' loads in flight before the stores (88 VGPRs) all measured within
+// the run-to-run spread or slower.
+#ifndef UGO_PKT_ENC_LANES
+#define UGO_PKT_ENC_LANES 32  // lanes per packet in phase B (32 or 64; the A/B is in DESIGN.md)
+#endif
+constexpr uint32_t kEncLanes = UGO_PKT_ENC_LANES;
+constexpr uint32_t kEncPacketsPerBlock = 64;  // phase A fills one wave
+static_assert(kEncLanes == 32 || kEncLanes == 64, "a half-wave or a wave per packet");
+
+enum : uint32_t {
+  kBadLargest = UGO_PKT_INCONSISTENT_LARGEST_ACKED,
+  kBadLowest = UGO_PKT_INCONSISTENT_LOWEST_ACKED,
+  kBadRangeCount = UGO_PKT_INCONSISTENT_RANGE_COUNT,
+};
+
+typedef uint32_t u32x4u __attribute__((ext_vector_type(4), aligned(1)));
+__device__ __forceinline__ u32x4 ldu16(const uint8_t* p) {  // 16 bytes at any byte address
+  return *reinterpret_cast<const u32x4u*>(p);
+}
+
+__device__ __forceinline__ uint32_t byte_of(const u32x4& v, uint32_t j) {
+  const uint32_t q = (j >> 2) & 3u;
+  const uint32_t d = (q & 2u) ? ((q & 1u) ? v.w : v.z) : ((q & 1u) ? v.y : v.x);
+  return (d >> (8u * (j & 3u))) & 0xffu;
+}
+
+// len(binary.PutUvarint(v))
+__device__ __forceinline__ uint32_t uvarint_len(uint64_t v) {
+  const uint32_t bits = 64u - static_cast<uint32_t>(__builtin_clzll(v | 1ull));
+  return (bits + 6u) / 7u;
+}
+
+// WriteUfloat16's 16-bit result
+__device__ __forceinline__ uint32_t ufloat16(uint64_t value) {
+  if (value < (1ull << 12)) return static_cast<uint32_t>(value);
+  if (value >= 0x3FFC0000000ull) return 0xFFFFu;  // uFloat16MaxValue
+  uint32_t exponent = 0;
+#pragma unroll
+  for (uint32_t offset = 16; offset > 0; offset /= 2) {
+    if (value >= (1ull << (11u + offset))) {
+      exponent += offset;
+      value >>= offset;
+    }
+  }
+  return (static_cast<uint32_t>(value) + (exponent << 11)) & 0xFFFFu;
+}
+
+// The packet's bytes in order, through a 16-byte window: a chunk is stored
+// (pad applied) when its last byte is put, or by finish() with zeros -- and
+// no pad -- past the packet's end.
+struct ByteWriter {
+  uint8_t* base;  // slot start
+  const uint8_t* pad;
+  uint32_t pos;
+  uint32_t w0, w1, w2, w3;
+
+  __device__ __forceinline__ void flush(uint32_t o, uint32_t keep) {
+    u32x4 v = {w0, w1, w2, w3};
+    if (pad) {
+      u32x4 k = *reinterpret_cast<const u32x4*>(pad + o);
+      if (keep < 16u) {
+        uint32_t m[4];
+#pragma unroll
+        for (uint32_t j = 0; j < 4; ++j) {
+          const uint32_t n = keep >= 4u * j + 4u ? 4u : (keep > 4u * j ? keep - 4u * j : 0u);
+          m[j] = n >= 4u ? 0xffffffffu : ((1u << (8u * n)) - 1u);
+        }
+        k &= u32x4{m[0], m[1], m[2], m[3]};
+      }
+      v ^= k;
+    }
+    *reinterpret_cast<u32x4*>(base + o) = v;
+    w0 = w1 = w2 = w3 = 0u;
+  }
+  __device__ __forceinline__ void put(uint32_t b) {
+    const uint32_t v = (b & 0xffu) << (8u * (pos & 3u));
+    const uint32_t q = (pos >> 2) & 3u;
+    w0 |= q == 0u ? v : 0u;
+    w1 |= q == 1u ? v : 0u;
+    w2 |= q == 2u ? v : 0u;
+    w3 |= q == 3u ? v : 0u;
+    if ((++pos & 15u) == 0u) flush(pos - 16u, 16u);
+  }
+  __device__ __forceinline__ void put_uvarint(uint64_t v) {  // at most 10 bytes
+    while (v >= 0x80u) {
+      put(static_cast<uint32_t>(v) | 0x80u);
+      v >>= 7;
+    }
+    put(static_cast<uint32_t>(v));
+  }
+  __device__ __forceinline__ void skip_chunks(uint32_t nbytes) { pos += nbytes; }  // window empty, pos % 16 == 0
+  __device__ __forceinline__ void finish() {
+    if (pos & 15u) flush(pos & ~15u, pos & 15u);
+  }
+};
+
+// One ACK range after the first, as sack.write sees it (packet.go:385-391):
+// its length and the number of blocks the writer emits for the gap before it.
+struct GapBlocks {
+  uint64_t length, gap, num;
+};
+__device__ __forceinline__ GapBlocks gap_blocks(uint64_t prev_first, uint64_t first, uint64_t last) {
+  GapBlocks g;
+  g.length = last - first + 1;
+  g.gap = prev_first - last - 1;
+  g.num = g.gap / 0xFFu + 1;
+  if (g.gap % 0xFFu == 0) --g.num;
+  return g;
+}
+
+// Sizes packet i and, if the reference would encode it and it fits, writes
+// its header and boundary chunks.  Returns the status; pos0 = where the first
+// segment header starts, ns = segments to place (0 unless the status is OK).
+__device__ uint32_t encode_header(const PktEncArgs& a, uint64_t i, uint32_t& pos0, uint32_t& ns, uint32_t& total) {
+  const ugo_pkt_info& I = a.info[i];
+  const uint32_t nr = I.n_ranges, nseg = I.n_segments;
+  if (nr > a.max_ranges || nseg > a.max_segments) return kCapacity;
+  const uint64_t* rg = a.ranges + i * 2ull * a.max_ranges;
+  const ugo_pkt_segment* sg = a.segs + i * a.max_segments;
+  const uint64_t pn = I.packet_number, sw = I.stop_waiting;
+  const uint64_t largest = I.largest_acked, in_order = I.largest_in_order;
+  const bool has_sack = (I.flags & 0x80u) != 0;  // p.sack != nil
+  const uint32_t flags = I.flags | (sw != 0 ? 0x40u : 0u) | (nseg != 0 ? 0x20u : 0u);
+  const uint32_t room = a.framed ? 6u : 0u;
+
+  // ---- size and status; every quantity is arithmetic in the field values
+  uint64_t len = room + 1u;
+  uint64_t num_ranges = 0, first_len = 0;
+  if (has_sack) {
+    len += 1u + uvarint_len(largest) + 2u;
+    if (nr != 0) {
+      // numWritableNackRanges: ceil((gap + 1) / 256) blocks per gap while they stay below 255
+      uint64_t num = 0;
+      for (uint32_t k = 1; k < nr; ++k) {
+        const uint64_t g1 = rg[2 * (k - 1)] - rg[2 * k + 1];
+        const uint64_t rl = g1 / 256u + (g1 % 256u != 0 ? 1u : 0u);
+        if (num + rl < 0xFFu)
+          num += rl;
+        else
+          break;
+      }
+      num_ranges = num + 1;
+      len += 1u;
+      if (largest != rg[1]) return kBadLargest;
+      if (in_order != rg[2 * (nr - 1)]) return kBadLowest;
+      first_len = largest - rg[0] + 1;
+    } else {
+      first_len = largest - in_order + 1;
+    }
+    len += uvarint_len(first_len);
+    uint64_t written = nr != 0 ? 1u : 0u;
+    for (uint32_t k = 1; k < nr; ++k) {
+      const GapBlocks g = gap_blocks(rg[2 * (k - 1)], rg[2 * k], rg[2 * k + 1]);
+      // written <= num_ranges <= 255 here, and the writer stops at the first
+      // range that reaches num_ranges: a range with more blocks than remain
+      // ends in "inconsistent number of ACK ranges written" whatever follows
+      if (g.num > num_ranges - written) return kBadRangeCount;
+      if (g.num != 0) len += 2u * (g.num - 1u) + 1u + uvarint_len(g.length);
+      written += g.num;
+      if (written >= num_ranges) break;
+    }
+    if (written != num_ranges) return kBadRangeCount;
+  }
+  if (flags != 0x80u) len += uvarint_len(pn);
+  if (sw != 0) len += uvarint_len(sw);
+  const uint64_t seg_start = len;
+  for (uint32_t j = 0; j < nseg; ++j) len += uvarint_len(sg[j].offset) + 2u + sg[j].len;
+  if (len > a.slot) return kCapacity;
+
+  // ---- write
+  ByteWriter w;
+  w.base = a.wire + i * a.slot;
+  w.pad = a.pad;
+  w.pos = room;  // framed: bytes [0, 6) stay zero for markData
+  w.w0 = w.w1 = w.w2 = w.w3 = 0u;
+  w.put(flags);
+  if (has_sack) {
+    w.put(nr != 0 ? 0x20u : 0u);
+    w.put_uvarint(largest);
+    const uint32_t d = ufloat16(I.delay_us);
+    w.put(d);  // utils.WriteUint16: little endian
+    w.put(d >> 8);
+    if (nr != 0) w.put(static_cast<uint32_t>(num_ranges - 1));
+    w.put_uvarint(first_len);
+    uint64_t written = nr != 0 ? 1u : 0u;
+    for (uint32_t k = 1; k < nr; ++k) {
+      const GapBlocks g = gap_blocks(rg[2 * (k - 1)], rg[2 * k], rg[2 * k + 1]);
+      // g.num <= 254 (checked above): the long-gap blocks are bounded by the
+      // block-count byte, not by the gap
+      for (uint32_t b = 1; b < static_cast<uint32_t>(g.num); ++b) {
+        w.put(0xFFu);
+        w.put(0u);
+      }
+      if (g.num != 0) {
+        w.put(g.num == 1 ? static_cast<uint32_t>(g.gap) : static_cast<uint32_t>(g.gap % 0xFFu));
+        w.put_uvarint(g.length);
+      }
+      written += g.num;
+      if (written >= num_ranges) break;
+    }
+  }
+  if (flags != 0x80u) w.put_uvarint(pn);
+  if (sw != 0) w.put_uvarint(sw);
+  for (uint32_t j = 0; j < nseg; ++j) {
+    const uint32_t L = sg[j].len;
+    w.put_uvarint(sg[j].offset);
+    w.put(L >> 8);  // binary.BigEndian uint16
+    w.put(L);
+    const uint8_t* src = a.payload + i * a.payload_stride + sg[j].data_off;
+    if (L < 16u) {
+      for (uint32_t k = 0; k < L; ++k) w.put(src[k]);
+      continue;
+    }
+    const uint32_t head = (16u - (w.pos & 15u)) & 15u;  // up to the next chunk boundary (< 16 <= L)
+    const uint32_t interior = (L - head) & ~15u;         // whole chunks: phase B
+    const uint32_t tail = L - head - interior;
+    const u32x4 H = ldu16(src), T = ldu16(src + L - 16u);
+    for (uint32_t k = 0; k < head; ++k) w.put(byte_of(H, k));
+    w.skip_chunks(interior);
+    for (uint32_t k = 0; k < tail; ++k) w.put(byte_of(T, 16u - tail + k));
+  }
+  w.finish();
+  pos0 = static_cast<uint32_t>(seg_start);
+  ns = nseg;
+  total = static_cast<uint32_t>(len);
+  return kOK;
+}
+
+__global__ __launch_bounds__(256) void k_packet_encode(PktEncArgs a) {
+  __shared__ uint32_t s_pos0[kEncPacketsPerBlock], s_ns[kEncPacketsPerBlock];
+  const uint64_t first = blockIdx.x * static_cast<uint64_t>(kEncPacketsPerBlock);
+  if (threadIdx.x < kEncPacketsPerBlock) {
+    const uint64_t i = first + threadIdx.x;
+    uint32_t pos0 = 0, ns = 0, total = 0;
+    if (i < a.npk) {
+      const uint32_t st = encode_header(a, i, pos0, ns, total);
+      a.status[i] = static_cast<uint8_t>(st);
+      a.wire_lens[i] = static_cast<uint16_t>(st == kOK ? total : 0u);
+    }
+    s_pos0[threadIdx.x] = pos0;
+    s_ns[threadIdx.x] = ns;
+  }
+  __syncthreads();
+  constexpr uint32_t kGroups = 256u / kEncLanes;
+  const uint32_t grp = threadIdx.x / kEncLanes, hl = threadIdx.x % kEncLanes;
+  for (uint32_t t = grp; t < kEncPacketsPerBlock; t += kGroups) {
+    const uint32_t ns = s_ns[t];  // 0: no packet, an error status, or no segment
+    if (ns == 0) continue;
+    const uint64_t i = first + t;
+    const ugo_pkt_segment* sg = a.segs + i * a.max_segments;
+    const uint8_t* pay = a.payload + i * a.payload_stride;
+    uint8_t* out = a.wire + i * a.slot;
+    uint32_t pos = s_pos0[t];
+    for (uint32_t j = 0; j < ns; ++j) {
+      const uint32_t L = sg[j].len;
+      pos += uvarint_len(sg[j].offset) + 2u;      // segment data at packet bytes [pos, pos + L)
+      const uint8_t* src = pay + sg[j].data_off;  // packet byte x of it is src[x - pos]
+      const uint32_t c0 = (pos + 15u) >> 4, c1 = (pos + L) >> 4;  // interior chunks [c0, c1)
+      for (uint32_t c = c0 + hl; c < c1; c += 4u * kEncLanes) {
+        u32x4 v[4];
+#pragma unroll
+        for (uint32_t q = 0; q < 4; ++q) {
+          const uint32_t cc = c + q * kEncLanes;
+          if (cc < c1) {
+            v[q] = ldu16(src + (16u * cc - pos));
+            if (a.pad) v[q] ^= *reinterpret_cast<const u32x4*>(a.pad + 16u * cc);
+          }
+        }
+#pragma unroll
+        for (uint32_t q = 0; q < 4; ++q) {
+          const uint32_t cc = c + q * kEncLanes;
+          if (cc < c1) __builtin_nontemporal_store(v[q], reinterpret_cast<u32x4*>(out + 16u * cc));
+        }
+      }
+      pos += L;
+    }
+  }
+}
+
 }  // namespace
 
 hipError_t launch_packet_decode(const PktArgs& a, hipStream_t s) {
   if (a.npk == 0) return hipSuccess;
   const uint64_t blocks = (a.npk + 255) / 256;
   launch(kKPacket, k_packet_decode, dim3(static_cast<uint32_t>(blocks)), dim3(256), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_packet_encode(const PktEncArgs& a, hipStream_t s) {
+  if (a.npk == 0) return hipSuccess;
+  const uint64_t blocks = (a.npk + kEncPacketsPerBlock - 1) / kEncPacketsPerBlock;
+  launch(kKPacketEncode, k_packet_encode, dim3(static_cast<uint32_t>(blocks)), dim3(256), 0, s, a);
   return hipGetLastError();
 }
 

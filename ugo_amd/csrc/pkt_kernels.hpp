@@ -1,4 +1,4 @@
-// pkt_kernels.hpp -- internal interface of the packet wire-codec decoder.
+// pkt_kernels.hpp -- internal interface of the packet wire codec (decoder and encoder).
 #pragma once
 #include <hip/hip_runtime_api.h>
 
@@ -24,6 +24,25 @@ struct PktArgs {
 };
 
 hipError_t launch_packet_decode(const PktArgs& a, hipStream_t s);
+
+struct PktEncArgs {
+  const ugo_pkt_info* info;
+  const uint64_t* ranges;       // [npk][max_ranges][2]
+  const ugo_pkt_segment* segs;  // [npk][max_segments]
+  const uint8_t* payload;       // segment j's bytes at payload + i*payload_stride + data_off (any alignment)
+  const uint8_t* pad;           // nullable keystream, >= slot bytes (null when framed)
+  uint8_t* wire;                // packet i at wire + i*slot (16-B aligned)
+  uint16_t* wire_lens;
+  uint8_t* status;
+  uint64_t npk;
+  uint64_t slot;
+  uint64_t payload_stride;
+  uint32_t max_ranges;
+  uint32_t max_segments;
+  uint32_t framed;
+};
+
+hipError_t launch_packet_encode(const PktEncArgs& a, hipStream_t s);
 
 }  // namespace kern
 }  // namespace ugo

@@ -2173,6 +2173,42 @@ int ugo_fec_packet_decode(ugo_fec* c, const uint8_t* pkts, size_t slot, const ui
   return hip_status(ugo::kern::launch_packet_decode(a, static_cast<hipStream_t>(stream)));
 }
 
+int ugo_fec_packet_encode(ugo_fec* c, const ugo_pkt_info* info, const uint64_t* ranges, size_t max_ranges,
+                          const ugo_pkt_segment* segs, size_t max_segments, const uint8_t* payload,
+                          size_t payload_stride, size_t npk, const uint8_t* pad, unsigned flags, uint8_t* wire,
+                          size_t slot, uint16_t* wire_lens, uint8_t* status, void* stream) {
+  if (!c) return UGO_FEC_ERR_INVALID_ARG;
+  if (c->poisoned) return UGO_FEC_ERR_HIP;
+  if (npk == 0) return UGO_FEC_OK;
+  if (!info || !wire || !wire_lens || !status || slot % 16 || slot == 0 || slot > 0xffff ||
+      reinterpret_cast<uintptr_t>(wire) % 16 || (pad && reinterpret_cast<uintptr_t>(pad) % 16) ||
+      (max_ranges && !ranges) || (max_segments && (!segs || !payload)) || max_ranges > 0xffff ||
+      max_segments > 0xffff || (flags & ~UGO_PKT_FEC_FRAMED) || ((flags & UGO_PKT_FEC_FRAMED) && pad))
+    return UGO_FEC_ERR_INVALID_ARG;
+  DeviceGuard g(c->device);
+  if (!g.ok) return UGO_FEC_ERR_NO_DEVICE;
+  if (!device_view(info) || !device_view(ranges) || !device_view(segs) || !device_view(payload) ||
+      !device_view(pad) || !device_view(wire) || !device_view(wire_lens) || !device_view(status))
+    return UGO_FEC_ERR_INVALID_ARG;
+  TimerScope ts(c);
+  ugo::kern::PktEncArgs a{};
+  a.info = info;
+  a.ranges = ranges;
+  a.segs = segs;
+  a.payload = payload;
+  a.pad = pad;
+  a.wire = wire;
+  a.wire_lens = wire_lens;
+  a.status = status;
+  a.npk = npk;
+  a.slot = slot;
+  a.payload_stride = payload_stride;
+  a.max_ranges = static_cast<uint32_t>(max_ranges);
+  a.max_segments = static_cast<uint32_t>(max_segments);
+  a.framed = flags & UGO_PKT_FEC_FRAMED;
+  return hip_status(ugo::kern::launch_packet_encode(a, static_cast<hipStream_t>(stream)));
+}
+
 int ugo_fec_rc4_keystream(const uint8_t* key, size_t key_len, uint8_t* out, size_t n) {
   if (!key || key_len == 0 || key_len > 256 || (n && !out)) return UGO_FEC_ERR_INVALID_ARG;
   ugo::rc4_keystream(key, key_len, out, n);

@@ -93,13 +93,17 @@ _lib = None
 
 # include/ugo_pkt.h
 PKT_FEC_FRAMED = 1
+PKT_CAPACITY = 6
+PKT_INCONSISTENT_LARGEST_ACKED = 7  # packet_encode's per-packet statuses
+PKT_INCONSISTENT_LOWEST_ACKED = 8
+PKT_INCONSISTENT_RANGE_COUNT = 9
 PKT_INFO_DTYPE = np.dtype([("packet_number", "<u8"), ("stop_waiting", "<u8"), ("largest_acked", "<u8"),
                            ("largest_in_order", "<u8"), ("delay_us", "<u8"), ("status", "<u4"),
                            ("payload_off", "<u4"), ("n_ranges", "<u2"), ("n_segments", "<u2"), ("flags", "u1"),
                            ("fec_flag_lo", "u1"), ("reserved", "u1", (10,))])
 # include/ugo_fec.h launch timing
 KERNEL_NAMES = {1: "encode", 2: "reconstruct", 3: "prepare", 4: "bytes", 5: "rx_assemble", 6: "tx_assemble",
-                7: "packet_decode"}
+                7: "packet_decode", 8: "packet_encode"}
 KERNEL_IDS = {v: k for k, v in KERNEL_NAMES.items()}
 LAUNCH_TIME_DTYPE = np.dtype([("kernel", "<u4"), ("ms", "<f4")])
 PKT_SEGMENT_DTYPE = np.dtype([("offset", "<u8"), ("data_off", "<u4"), ("len", "<u2"), ("avail", "<u2")])
@@ -142,6 +146,7 @@ def load_library(path: str = LIB_PATH):
     lib.ugo_fec_rc4_keystream.argtypes = [vp, sz, vp, sz]
     lib.ugo_fec_tx_assemble.argtypes = [vp, vp, sz, vp, sz, ctypes.c_uint32, vp, sz, vp, sz, vp, vp, vp]
     lib.ugo_fec_packet_decode.argtypes = [vp, vp, sz, vp, sz, vp, u, vp, vp, sz, vp, sz, vp]
+    lib.ugo_fec_packet_encode.argtypes = [vp, vp, vp, sz, vp, sz, vp, sz, sz, vp, u, vp, sz, vp, vp, vp]
     lib.ugo_fec_reconstruct_rows.argtypes = [vp, vp, vp, sz, sz, vp, sz, sz, u, vp, vp]
     lib.ugo_fec_lossy_groups.argtypes = [vp, vp, sz, u, vp, vp, vp]
     lib.ugo_fec_rx_recover_host.argtypes = [vp, vp, sz, vp, sz, vp, ctypes.c_uint64, sz, sz, vp, vp, vp, sz, sz, vp,
@@ -523,6 +528,45 @@ class Encoder:
             PKT_FEC_FRAMED if framed else 0, info.data_ptr(), ranges.data_ptr(), max_ranges, segs.data_ptr(),
             max_segments, _stream_handle(stream)))
         return info, ranges, segs
+
+    def packet_encode(self, info, ranges, segs, payload, slot: int, payload_stride: int = 0, pad=None,
+                      framed: bool = False, stream=None, out=None):
+        """Batch ugoPacket.encode (include/ugo_pkt.h ugo_fec_packet_encode), the
+        reverse of packet_decode: info = uint8 CUDA [npk, 64] (PKT_INFO_DTYPE),
+        ranges = int64 CUDA [npk, max_ranges, 2], segs = uint8 CUDA [npk,
+        max_segments, 16] (PKT_SEGMENT_DTYPE); segment data is read from payload
+        (uint8 CUDA, any alignment) at i*payload_stride + data_off.  framed: 6 B
+        of zeroed header room in front (tx_assemble's input; pad must be None);
+        else pad = uint8 CUDA keystream (>= slot bytes) or None.  Returns CUDA
+        tensors (wire uint8 [npk, slot], wire_lens int16 [npk], status uint8
+        [npk]); out = such a triple to reuse.  Only bytes [0, round_up(len, 16))
+        of a slot are written."""
+        npk = info.shape[0]
+        _require(info.is_contiguous() and info.element_size() == 1 and tuple(info.shape) == (npk, 64))
+        _require(ranges.is_contiguous() and ranges.element_size() == 8 and ranges.dim() == 3 and
+                 ranges.shape[0] == npk and ranges.shape[2] == 2)
+        _require(segs.is_contiguous() and segs.element_size() == 1 and segs.dim() == 3 and segs.shape[0] == npk and
+                 segs.shape[2] == 16)
+        _require(payload.is_contiguous() and payload.element_size() == 1)
+        _require(not (framed and pad is not None), "framed packets are encrypted by tx_assemble: pad must be None")
+        if pad is not None:
+            _require(pad.is_contiguous() and pad.element_size() == 1 and pad.numel() >= slot)
+        if out is not None:
+            wire, wire_lens, status = out
+            _require(tuple(wire.shape) == (npk, slot) and wire.is_contiguous() and wire.element_size() == 1)
+            _require(wire_lens.numel() == npk and wire_lens.element_size() == 2 and wire_lens.is_contiguous())
+            _require(status.numel() == npk and status.element_size() == 1 and status.is_contiguous())
+        else:
+            dev = info.device
+            wire = torch.zeros((npk, slot), dtype=torch.uint8, device=dev)
+            wire_lens = torch.zeros(npk, dtype=torch.int16, device=dev)
+            status = torch.zeros(npk, dtype=torch.uint8, device=dev)
+        _raise(load_library().ugo_fec_packet_encode(
+            self._h, info.data_ptr(), ranges.data_ptr(), ranges.shape[1], segs.data_ptr(), segs.shape[1],
+            payload.data_ptr(), payload_stride, npk, None if pad is None else pad.data_ptr(),
+            PKT_FEC_FRAMED if framed else 0, wire.data_ptr(), slot, wire_lens.data_ptr(), status.data_ptr(),
+            _stream_handle(stream)))
+        return wire, wire_lens, status
 
     # ---------------------------------------------------------- launch timing
     def timing_begin(self, max_launches: int):

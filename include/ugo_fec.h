@@ -63,7 +63,9 @@ extern "C" {
  *    queues per process, see ugo_fec_set_host_copy_queue).
  *    Added without a version change (new symbols and values only):
  *    ugo_fec_packet_encode with ugo_pkt_status 7-9 (ugo_pkt.h) and
- *    UGO_FEC_KERNEL_PACKET_ENCODE. */
+ *    UGO_FEC_KERNEL_PACKET_ENCODE; the ugo_fec_stream_* entry points with
+ *    ugo_stream_status (ugo_stream.h), UGO_FEC_KERNEL_STREAM_DELIVER and
+ *    UGO_FEC_KERNEL_STREAM_READ. */
 #define UGO_FEC_ABI_VERSION 9
 
 /* Status codes.  1..5 map 1:1 onto the klauspost/reedsolomon error values
@@ -463,6 +465,8 @@ int ugo_fec_rc4_keystream(const uint8_t* key, size_t key_len, uint8_t* out, size
 #define UGO_FEC_KERNEL_TX 6          /* ugo_fec_tx_assemble                     */
 #define UGO_FEC_KERNEL_PACKET 7      /* ugo_fec_packet_decode                   */
 #define UGO_FEC_KERNEL_PACKET_ENCODE 8 /* ugo_fec_packet_encode                 */
+#define UGO_FEC_KERNEL_STREAM_DELIVER 9 /* ugo_fec_stream_deliver (ugo_stream.h)  */
+#define UGO_FEC_KERNEL_STREAM_READ 10   /* ugo_fec_stream_read                    */
 
 typedef struct ugo_fec_launch_time {
   uint32_t kernel; /* UGO_FEC_KERNEL_* */

@@ -26,6 +26,8 @@ enum KernelId : uint32_t {
   kKTx = 6,           // TX group assembly
   kKPacket = 7,       // packet wire decode
   kKPacketEncode = 8, // packet wire encode
+  kKStreamDeliver = 9,  // stream delivery (batch handleSegment)
+  kKStreamRead = 10,    // stream read (Conn.Read)
 };
 
 struct LaunchTimer {

@@ -30,6 +30,7 @@
 #include "rx_kernels.hpp"
 #include "tx_kernels.hpp"
 #include "pkt_kernels.hpp"
+#include "stream_kernels.hpp"
 
 namespace {
 
@@ -2207,6 +2208,135 @@ int ugo_fec_packet_encode(ugo_fec* c, const ugo_pkt_info* info, const uint64_t* 
   a.max_segments = static_cast<uint32_t>(max_segments);
   a.framed = flags & UGO_PKT_FEC_FRAMED;
   return hip_status(ugo::kern::launch_packet_encode(a, static_cast<hipStream_t>(stream)));
+}
+
+// ---------------------------------------------------------------- stream delivery (include/ugo_stream.h)
+struct ugo_stream_rx {
+  ugo_fec* ctx = nullptr;
+  size_t cap = 0;
+  uint8_t* win = nullptr;
+  unsigned long long* bits = nullptr;  // C | S | claim | contested, cap / 64 words each
+  ugo::kern::StreamRecord* rec = nullptr;
+  hipStream_t last = nullptr;  // the stream of the last deliver / read
+};
+
+int ugo_fec_stream_rx_create(ugo_fec* c, size_t window_bytes, ugo_stream_rx** out) {
+  static_assert(sizeof(ugo_stream_rx_state) == 96, "ugo_stream_rx_state is 96 bytes");
+  static_assert(UGO_FEC_KERNEL_STREAM_DELIVER == ugo::kern::kKStreamDeliver &&
+                    UGO_FEC_KERNEL_STREAM_READ == ugo::kern::kKStreamRead,
+                "kernel classes match the header");
+  if (out) *out = nullptr;
+  if (!c || !out || window_bytes < UGO_STREAM_MIN_WINDOW || (window_bytes & (window_bytes - 1)) != 0)
+    return UGO_FEC_ERR_INVALID_ARG;
+  if (c->poisoned) return UGO_FEC_ERR_HIP;
+  DeviceGuard g(c->device);
+  if (!g.ok) return UGO_FEC_ERR_NO_DEVICE;
+  ugo_stream_rx* rx = new (std::nothrow) ugo_stream_rx();
+  if (!rx) return UGO_FEC_ERR_HIP;
+  rx->ctx = c;
+  rx->cap = window_bytes;
+  const size_t bitmap_bytes = window_bytes / 8;
+  ugo::kern::StreamRecord init;
+  ugo::kern::stream_record_init(&init);
+  if (hipMalloc(&rx->win, window_bytes) != hipSuccess || hipMalloc(&rx->bits, 4 * bitmap_bytes) != hipSuccess ||
+      hipMalloc(&rx->rec, sizeof(init)) != hipSuccess || hipMemset(rx->win, 0, window_bytes) != hipSuccess ||
+      hipMemset(rx->bits, 0, 4 * bitmap_bytes) != hipSuccess ||
+      hipMemcpy(rx->rec, &init, sizeof(init), hipMemcpyHostToDevice) != hipSuccess ||
+      hipStreamSynchronize(nullptr) != hipSuccess) {  // the fills ran on the null stream
+    (void)hipGetLastError();
+    ugo_fec_stream_rx_destroy(rx);
+    return UGO_FEC_ERR_HIP;
+  }
+  *out = rx;
+  return UGO_FEC_OK;
+}
+
+void ugo_fec_stream_rx_destroy(ugo_stream_rx* rx) {
+  if (!rx) return;
+  {
+    DeviceGuard g(rx->ctx->device);
+    if (rx->last) (void)hipStreamSynchronize(rx->last);
+    (void)hipFree(rx->win);
+    (void)hipFree(rx->bits);
+    (void)hipFree(rx->rec);
+  }
+  delete rx;
+}
+
+int ugo_fec_stream_deliver(ugo_stream_rx* rx, const uint8_t* pkts, size_t slot, const uint8_t* pad,
+                           const ugo_pkt_info* info, const ugo_pkt_segment* segs, size_t max_segments, size_t npk,
+                           uint8_t* seg_status, void* stream) {
+  if (!rx) return UGO_FEC_ERR_INVALID_ARG;
+  ugo_fec* c = rx->ctx;
+  if (c->poisoned) return UGO_FEC_ERR_HIP;
+  if (npk == 0) return UGO_FEC_OK;
+  if (!pkts || !info || !segs || !seg_status || slot % 16 || slot == 0 || slot > 0xffff ||
+      reinterpret_cast<uintptr_t>(pkts) % 16 || (pad && reinterpret_cast<uintptr_t>(pad) % 16) ||
+      max_segments == 0 || max_segments > 0xffff || npk > (size_t(1) << 31))
+    return UGO_FEC_ERR_INVALID_ARG;
+  DeviceGuard g(c->device);
+  if (!g.ok) return UGO_FEC_ERR_NO_DEVICE;
+  if (!device_view(pkts) || !device_view(pad) || !device_view(info) || !device_view(segs) ||
+      !device_view(seg_status))
+    return UGO_FEC_ERR_INVALID_ARG;
+  TimerScope ts(c);
+  const size_t words = rx->cap / 64;
+  ugo::kern::StreamArgs a{};
+  a.pkts = pkts;
+  a.pad = pad;
+  a.info = info;
+  a.segs = segs;
+  a.seg_status = seg_status;
+  a.win = rx->win;
+  a.C = rx->bits;
+  a.S = rx->bits + words;
+  a.claim = rx->bits + 2 * words;
+  a.cont = rx->bits + 3 * words;
+  a.rec = rx->rec;
+  a.npk = npk;
+  a.slot = slot;
+  a.cap = rx->cap;
+  a.max_segments = static_cast<uint32_t>(max_segments);
+  rx->last = static_cast<hipStream_t>(stream);
+  return hip_status(ugo::kern::launch_stream_deliver(a, rx->last));
+}
+
+int ugo_fec_stream_read(ugo_stream_rx* rx, uint8_t* dst, size_t n, uint64_t* n_read, uint8_t* eof, void* stream) {
+  if (!rx || !n_read) return UGO_FEC_ERR_INVALID_ARG;
+  ugo_fec* c = rx->ctx;
+  if (c->poisoned) return UGO_FEC_ERR_HIP;
+  DeviceGuard g(c->device);
+  if (!g.ok) return UGO_FEC_ERR_NO_DEVICE;
+  if (!device_view(dst) || !device_view(n_read) || !device_view(eof)) return UGO_FEC_ERR_INVALID_ARG;
+  TimerScope ts(c);
+  const size_t words = rx->cap / 64;
+  ugo::kern::StreamReadArgs a{};
+  a.win = rx->win;
+  a.C = rx->bits;
+  a.S = rx->bits + words;
+  a.rec = rx->rec;
+  a.dst = dst;
+  a.n_read = reinterpret_cast<unsigned long long*>(n_read);
+  a.eof = eof;
+  a.n = n;
+  a.cap = rx->cap;
+  rx->last = static_cast<hipStream_t>(stream);
+  return hip_status(ugo::kern::launch_stream_read(a, rx->last));
+}
+
+int ugo_fec_stream_rx_state(ugo_stream_rx* rx, ugo_stream_rx_state* host_out) {
+  if (!rx || !host_out) return UGO_FEC_ERR_INVALID_ARG;
+  DeviceGuard g(rx->ctx->device);
+  if (!g.ok) return UGO_FEC_ERR_NO_DEVICE;
+  if (hipStreamSynchronize(rx->last) != hipSuccess) return UGO_FEC_ERR_HIP;
+  return hip_status(hipMemcpy(host_out, &rx->rec->pub, sizeof(*host_out), hipMemcpyDeviceToHost));
+}
+
+int ugo_fec_stream_rx_window(ugo_stream_rx* rx, uint8_t** window_dev, size_t* window_bytes) {
+  if (!rx || !window_dev || !window_bytes) return UGO_FEC_ERR_INVALID_ARG;
+  *window_dev = rx->win;
+  *window_bytes = rx->cap;
+  return UGO_FEC_OK;
 }
 
 int ugo_fec_rc4_keystream(const uint8_t* key, size_t key_len, uint8_t* out, size_t n) {

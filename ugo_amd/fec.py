@@ -41,6 +41,7 @@ LIB_PATH = os.environ.get("UGO_FEC_LIB") or os.path.join(_HERE, "libugofec.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ugo_fec.h")
 CONN_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ugo_fec_conn.h")
 PKT_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ugo_pkt.h")
+STREAM_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ugo_stream.h")
 
 OK = 0
 RECONSTRUCT_DATA_ONLY = 1
@@ -103,11 +104,26 @@ PKT_INFO_DTYPE = np.dtype([("packet_number", "<u8"), ("stop_waiting", "<u8"), ("
                            ("fec_flag_lo", "u1"), ("reserved", "u1", (10,))])
 # include/ugo_fec.h launch timing
 KERNEL_NAMES = {1: "encode", 2: "reconstruct", 3: "prepare", 4: "bytes", 5: "rx_assemble", 6: "tx_assemble",
-                7: "packet_decode", 8: "packet_encode"}
+                7: "packet_decode", 8: "packet_encode", 9: "stream_deliver", 10: "stream_read"}
 KERNEL_IDS = {v: k for k, v in KERNEL_NAMES.items()}
 LAUNCH_TIME_DTYPE = np.dtype([("kernel", "<u4"), ("ms", "<f4")])
 PKT_SEGMENT_DTYPE = np.dtype([("offset", "<u8"), ("data_off", "<u4"), ("len", "<u2"), ("avail", "<u2")])
 assert PKT_INFO_DTYPE.itemsize == 64 and PKT_SEGMENT_DTYPE.itemsize == 16
+# include/ugo_stream.h: ugo_stream_status (per segment; the last two are the connection's err) and the record
+STREAM_NONE = 0
+STREAM_ACCEPTED = 1
+STREAM_DUPLICATE = 2
+STREAM_OUT_OF_WINDOW = 3
+STREAM_OVERLAP = 4
+STREAM_TOO_MANY_GAPS = 5
+STREAM_MAX_GAPS = 50
+STREAM_MIN_WINDOW = 4096
+STREAM_STATE_DTYPE = np.dtype([("read_pos", "<u8"), ("head_off", "<u8"), ("hi", "<u8"), ("readable", "<u8"),
+                               ("accepted", "<u8"), ("duplicate", "<u8"), ("out_of_window", "<u8"),
+                               ("skipped_packets", "<u8"), ("ordered_segments", "<u8"), ("err_packet", "<u8"),
+                               ("err_segment", "<u4"), ("err", "<u4"), ("ngaps", "<u4"), ("head_valid", "u1"),
+                               ("eof", "u1"), ("reserved", "u1", (2,))])
+assert STREAM_STATE_DTYPE.itemsize == 96
 
 
 def load_library(path: str = LIB_PATH):
@@ -147,6 +163,13 @@ def load_library(path: str = LIB_PATH):
     lib.ugo_fec_tx_assemble.argtypes = [vp, vp, sz, vp, sz, ctypes.c_uint32, vp, sz, vp, sz, vp, vp, vp]
     lib.ugo_fec_packet_decode.argtypes = [vp, vp, sz, vp, sz, vp, u, vp, vp, sz, vp, sz, vp]
     lib.ugo_fec_packet_encode.argtypes = [vp, vp, vp, sz, vp, sz, vp, sz, sz, vp, u, vp, sz, vp, vp, vp]
+    lib.ugo_fec_stream_rx_create.argtypes = [vp, sz, ctypes.POINTER(vp)]
+    lib.ugo_fec_stream_rx_destroy.argtypes = [vp]
+    lib.ugo_fec_stream_rx_destroy.restype = None
+    lib.ugo_fec_stream_deliver.argtypes = [vp, vp, sz, vp, vp, vp, sz, sz, vp, vp]
+    lib.ugo_fec_stream_read.argtypes = [vp, vp, sz, vp, vp, vp]
+    lib.ugo_fec_stream_rx_state.argtypes = [vp, vp]
+    lib.ugo_fec_stream_rx_window.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(sz)]
     lib.ugo_fec_reconstruct_rows.argtypes = [vp, vp, vp, sz, sz, vp, sz, sz, u, vp, vp]
     lib.ugo_fec_lossy_groups.argtypes = [vp, vp, sz, u, vp, vp, vp]
     lib.ugo_fec_rx_recover_host.argtypes = [vp, vp, sz, vp, sz, vp, ctypes.c_uint64, sz, sz, vp, vp, vp, sz, sz, vp,
@@ -163,8 +186,8 @@ def load_library(path: str = LIB_PATH):
     return lib
 
 
-def header_symbols(paths=(HEADER_PATH, CONN_HEADER_PATH, PKT_HEADER_PATH)) -> List[str]:
-    """Every entry point declared in include/ugo_fec.h, ugo_fec_conn.h and ugo_pkt.h."""
+def header_symbols(paths=(HEADER_PATH, CONN_HEADER_PATH, PKT_HEADER_PATH, STREAM_HEADER_PATH)) -> List[str]:
+    """Every entry point declared in include/ugo_fec.h, ugo_fec_conn.h, ugo_pkt.h and ugo_stream.h."""
     out = set()
     for path in paths:
         src = open(path).read()
@@ -686,6 +709,102 @@ class Encoder:
 
     def ReconstructData(self, shards: list) -> None:
         self._reconstruct(shards, data_only=True)
+
+
+class _DeviceBytes:
+    """A span of device memory for torch.as_tensor (__cuda_array_interface__)."""
+
+    def __init__(self, ptr: int, nbytes: int, owner):
+        self.__cuda_array_interface__ = {"shape": (nbytes,), "typestr": "|u1", "data": (ptr, False), "version": 2}
+        self._owner = owner
+
+
+class StreamRx:
+    """A connection's receive window on the GPU (include/ugo_stream.h): batch
+    Conn.handleSegment (deliver) and Conn.Read (read) behind packet_decode."""
+
+    def __init__(self, enc: Encoder, window_bytes: int):
+        self.check_window(window_bytes)
+        h = ctypes.c_void_p()
+        _raise(load_library().ugo_fec_stream_rx_create(enc._h, window_bytes, ctypes.byref(h)))
+        self._h, self._enc = h, enc  # the context must outlive the window
+        self.window_bytes = window_bytes
+        self.device = enc.device
+
+    @staticmethod
+    def check_window(window_bytes: int):
+        _require(window_bytes >= STREAM_MIN_WINDOW and window_bytes & (window_bytes - 1) == 0,
+                 f"window_bytes must be a power of two >= {STREAM_MIN_WINDOW}")
+
+    @staticmethod
+    def check_batch(slot: int, pkts_ptr: int, pad_ptr: Optional[int]):
+        _require(slot % 16 == 0 and 0 < slot <= 0xffff, "slot must be a multiple of 16, at most 0xffff")
+        _require(pkts_ptr % 16 == 0 and (pad_ptr is None or pad_ptr % 16 == 0), "pkts and pad must be 16-B aligned")
+
+    def close(self):
+        if getattr(self, "_h", None):
+            load_library().ugo_fec_stream_rx_destroy(self._h)
+            self._h = None
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def deliver(self, pkts, info, segs, pad=None, stream=None, out=None):
+        """ugo_fec_stream_deliver: pkts = uint8 CUDA [npk, slot] (still encrypted),
+        info / segs as packet_decode returned them, pad = the decoder's keystream
+        or None.  Returns seg_status, uint8 CUDA [npk, max_segments] of STREAM_*
+        (out = such a tensor to reuse).  Nothing is synchronised."""
+        npk, slot = pkts.shape
+        _require(pkts.is_contiguous() and pkts.element_size() == 1)
+        _require(info.is_contiguous() and info.element_size() == 1 and tuple(info.shape) == (npk, 64))
+        _require(segs.is_contiguous() and segs.element_size() == 1 and segs.dim() == 3 and segs.shape[0] == npk and
+                 segs.shape[2] == 16)
+        if pad is not None:
+            _require(pad.is_contiguous() and pad.element_size() == 1 and pad.numel() >= slot)
+        self.check_batch(slot, pkts.data_ptr(), None if pad is None else pad.data_ptr())
+        max_segments = segs.shape[1]
+        if out is None:
+            out = torch.empty((npk, max_segments), dtype=torch.uint8, device=pkts.device)
+        _require(tuple(out.shape) == (npk, max_segments) and out.is_contiguous() and out.element_size() == 1)
+        _raise(load_library().ugo_fec_stream_deliver(
+            self._h, pkts.data_ptr(), slot, None if pad is None else pad.data_ptr(), info.data_ptr(),
+            segs.data_ptr(), max_segments, npk, out.data_ptr(), _stream_handle(stream)))
+        return out
+
+    def read(self, n: int, out=None, discard: bool = False, stream=None):
+        """ugo_fec_stream_read, Conn.Read(p[:n]) that never waits.  Returns CUDA
+        tensors (buf uint8 [n] -- None with discard --, n_read int64 [1], eof uint8
+        [1]): buf[:n_read] holds the bytes.  Nothing is synchronised."""
+        _require(n >= 0)
+        dev = torch.device("cuda", self.device)
+        if discard:
+            out = None
+        elif out is None:
+            out = torch.empty(max(n, 1), dtype=torch.uint8, device=dev)
+        if out is not None:
+            _require(out.is_contiguous() and out.element_size() == 1 and out.numel() >= n)
+        n_read = torch.zeros(1, dtype=torch.int64, device=dev)
+        eof = torch.zeros(1, dtype=torch.uint8, device=dev)
+        _raise(load_library().ugo_fec_stream_read(self._h, None if out is None else out.data_ptr(), n,
+                                                  n_read.data_ptr(), eof.data_ptr(), _stream_handle(stream)))
+        return out, n_read, eof
+
+    def state(self) -> np.ndarray:
+        """The connection's record (STREAM_STATE_DTYPE scalar); waits for the last deliver / read."""
+        out = np.zeros(1, STREAM_STATE_DTYPE)
+        _raise(load_library().ugo_fec_stream_rx_state(self._h, out.ctypes.data))
+        return out[0]
+
+    def window(self):
+        """The window as a uint8 CUDA tensor [window_bytes] over the device memory
+        itself (stream byte x at index x & (window_bytes - 1)); valid while this
+        object lives."""
+        p, n = ctypes.c_void_p(), ctypes.c_size_t()
+        _raise(load_library().ugo_fec_stream_rx_window(self._h, ctypes.byref(p), ctypes.byref(n)))
+        return torch.as_tensor(_DeviceBytes(p.value, n.value, self), device=torch.device("cuda", self.device))
 
 
 def rc4_keystream(key: bytes, n: int) -> bytes:

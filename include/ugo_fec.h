@@ -346,7 +346,8 @@ int ugo_fec_rx_assemble(ugo_fec* ctx, const uint8_t* wire, size_t slot_stride, c
  * (calcECC's window starts at offset 6, ugo/fec.go:228-236, ugo/conn.go:670).
  * Every other rule (flags, window, first copy wins, presence, stats, scratch)
  * as ugo_fec_rx_assemble; each row slot must span round_up(shard_size + 6, 16)
- * bytes.  A packet chunk lands at the offset it was read from, so the kernel
+ * bytes, and a placed row is written in [0, round_up(shard_size + 6, 16)) and
+ * nowhere else, whatever the alignment of the base and the strides.  A packet chunk lands at the offset it was read from, so the kernel
  * needs no byte realignment.  Recovery: run any reconstruct entry point on the
  * frame batch with shard size shard_size + 6.  GF(2^8) columns are
  * independent, so payload columns of a recovered row are bit-identical to the
@@ -376,7 +377,12 @@ int ugo_fec_rx_assemble_frames(ugo_fec* ctx, const uint8_t* wire, size_t slot_st
  * data packets go out and no parity does (status UGO_FEC_ERR_SHARD_NO_DATA,
  * parity wire_lens 0); the batch still spends d+p seqids on it, where the
  * reference's counter would move by d.  slot_in, slot_out: multiples of 16, >= round_up(max_len, 16);
- * d <= 32. */
+ * d <= 32.
+ * Write extent: a wire slot is written only in [0, round_up(wire_len, 16)),
+ * and its bytes [wire_len, round_up(wire_len, 16)) are zero; the rest of the
+ * slot, up to slot_out, keeps the caller's bytes.  A slot whose wire_len comes
+ * back 0 is not written at all: every slot of a bad-length group, and the
+ * parity slots of a header-only group.  pkts and lens are only read. */
 int ugo_fec_tx_assemble(ugo_fec* ctx, const uint8_t* pkts, size_t slot_in, const uint16_t* lens,
                         size_t groups, uint32_t first_seq, const uint8_t* pad, size_t max_len,
                         uint8_t* wire, size_t slot_out, uint16_t* wire_lens, int8_t* status,

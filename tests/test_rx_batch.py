@@ -19,6 +19,8 @@ from hypothesis import strategies as st
 import fec_ref
 import rc4_ref
 import rs_ref
+from assembly_image import expected_placement as _expected_placement
+from assembly_image import ring as _ring
 from ugo_amd import fec
 
 KEY = b"1234567890123456"  # ugo/listener.go:92, ugo/dial.go:132
@@ -30,55 +32,6 @@ def test_rc4_known_answers_and_product_keystream():
     assert rc4_ref.xor_stream(b"Secret", b"Attack at dawn").hex() == "45a01f645fc35b383552544b9bf5"
     for key in (b"Key", b"Wiki", KEY):
         assert fec.rc4_keystream(key, 1536) == rc4_ref.keystream(key, 1536)
-
-
-def _expected_placement(wire, G, n, S, pitch, first_group, frames=False):
-    """The batch ugo's per-packet path builds from `wire` in ring order
-    (decrypted packets): FEC.decode (ugo/fec.go:78-89), the flag filter of
-    Conn.handlePacket (ugo/conn.go:395), the group/slot of input
-    (ugo/fec.go:145,175), and its dedupe -- a seqid already queued drops the
-    new packet, so the first copy stays (ugo/fec.go:123-129).  Returns the
-    group-major batch, presence masks and stats [accepted, bad flag, out of
-    window, too short, duplicate].  frames: a row holds the decrypted packet's
-    first S + 6 bytes (ugo_fec_rx_assemble_frames: header, then the payload
-    at column 6) instead of its payload."""
-    want = np.zeros((G, n, pitch), np.uint8)
-    masks = np.zeros(G, np.uint64)
-    stats = [0, 0, 0, 0, 0]
-    seen = set()
-    for w in wire:
-        if len(w) < 6:
-            stats[3] += 1
-            continue
-        seq = int.from_bytes(w[:4], "little")
-        flag = int.from_bytes(w[4:6], "little")
-        if flag not in (0xF1, 0xF2):
-            stats[1] += 1
-            continue
-        g = seq // n - first_group
-        if not 0 <= g < G:
-            stats[2] += 1
-            continue
-        if seq in seen:
-            stats[4] += 1
-            continue
-        seen.add(seq)
-        stats[0] += 1
-        pl = w[:S + 6] if frames else w[6:6 + S]
-        want[g, seq % n, :] = 0
-        want[g, seq % n, :len(pl)] = np.frombuffer(pl, np.uint8)
-        masks[g] |= np.uint64(1 << (seq % n))
-    return want, masks, stats
-
-
-def _ring(wire, slot):
-    npk = len(wire)
-    slots = np.zeros((npk, slot), np.uint8)
-    lens = np.zeros(npk, np.uint16)
-    for i, w in enumerate(wire):
-        slots[i, :len(w)] = np.frombuffer(w, np.uint8)
-        lens[i] = len(w)
-    return slots, lens
 
 
 def _packets(groups, seed, full_len):

@@ -342,7 +342,10 @@ __global__ __launch_bounds__(256) void k_rx_place_h(RxArgs a) {
 // one, a tie (4 bench runs: -4.0 / -4.0 / +1.3 / +2.8 % in order, within 0.6 %
 // shuffled; profiles/r6/rx_frames/final_tree_runs.json); residency 3 blocks/CU (0.512 vs 0.539-0.553 ms at
 // 5 or uncapped, pitch 1488); rows at a 64-B pitch written to whole lines
-// (1536 for S = 1470: 0.40-0.46 vs 0.51-0.55 ms at the 1488 pitch); the same
+// (1536 for S = 1470: 0.40-0.46 vs 0.51-0.55 ms at the 1488 pitch -- a.fill =
+// round_up(S + 6, 64), which only the engine's own scratch rows get now: the
+// public calls write [0, round_up(S + 6, 16)) as include/ugo_fec.h says, the
+// bytes behind that being the caller's or nobody's); the same
 // frames one chunk per thread over the whole ring (the P2 shape, every lane
 // loading its packet's header and length) 0.58-0.63 ms -- a dependent header
 // load per lane outweighs the cheaper store pattern

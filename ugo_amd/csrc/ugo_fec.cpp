@@ -1077,17 +1077,18 @@ int host_path(ugo_fec* c, uint8_t* shards, const uint64_t* present, size_t group
   return UGO_FEC_OK;
 }
 
-// Bytes a frame row is written to: round_up(S + 6, 16), or -- when the row
-// slots are 64-B aligned and span it -- round_up(S + 6, 64): a row then ends on
-// a whole 64-B line instead of leaving its last line partially written (which
-// the neighbouring row's writer completes at another time).
-#ifndef UGO_RX_FRAME_FILL64
-#define UGO_RX_FRAME_FILL64 1
-#endif
-size_t rx_frame_fill(const uint8_t* shards, size_t S, size_t rstride, size_t gstride, size_t rows, size_t groups) {
-  const size_t w16 = round_up(S + 6, 16), w64 = round_up(S + 6, 64);
-  if (!UGO_RX_FRAME_FILL64 || reinterpret_cast<uintptr_t>(shards) % 64 || rstride % 64 || gstride % 64) return w16;
-  return layout_disjoint(w64, rstride, rows, gstride, groups) ? w64 : w16;
+// Bytes a placed row is written to.  The public calls write a frame row in
+// [0, round_up(S + 6, 16)) and nowhere else (include/ugo_fec.h), whatever the
+// alignment of the base and the strides: a caller may own no byte past that,
+// inside a wider pitch or behind the batch's last row.  own_lines: the caller
+// is the engine itself, the rows are its own scratch on 64-B aligned slots that
+// span round_up(S + 6, 64), and it asks for whole 64-B lines -- a row then ends
+// on a whole line instead of leaving its last one partially written (which the
+// neighbouring row's writer completes at another time).  Requested, never
+// inferred from pointer arithmetic: aligned, disjoint slots do not prove that
+// the bytes behind a row are the caller's.
+size_t rx_row_fill(size_t S, bool frame, bool own_lines) {
+  return round_up(frame ? S + 6 : S, frame && own_lines ? 64 : 16);
 }
 
 // Stream-ordered scratch of one rx_assemble call: presence snapshot [groups] u64 | claim words
@@ -1100,10 +1101,11 @@ size_t rx_scratch_bytes(const ugo_fec* c, size_t groups) {
 int rx_assemble_dev(ugo_fec* c, const uint8_t* wire, size_t slot_stride, const uint16_t* lens, size_t npk,
                     const uint8_t* pad, uint64_t first_group, size_t groups, uint8_t* shards, size_t S,
                     size_t row_stride, size_t group_stride, uint64_t* present, uint32_t* stats, hipStream_t s,
-                    bool frame = false, void* call_scratch = nullptr) {
+                    bool frame = false, void* call_scratch = nullptr, bool own_lines = false) {
   ugo::kern::RxArgs a{};
   a.frame = frame ? 1u : 0u;
-  a.fill = static_cast<uint32_t>(rx_frame_fill(shards, S, row_stride, group_stride, size_t(c->n), groups));
+  // the frame kernels' pass count follows this (launch_rx_scatter)
+  a.fill = static_cast<uint32_t>(rx_row_fill(S, frame, own_lines));
   a.wire = wire;
   a.lens = lens;
   a.pad = pad;
@@ -1837,7 +1839,8 @@ int ugo_fec_rx_recover_host(ugo_fec* c, const uint8_t* wire, size_t slot_stride,
   // payload at column 6; the recovery then runs over the frame window (GF columns are independent) and
   // only the payload columns of a recovered row come back
   const size_t fo = kRxFrames ? 6 : 0, FS = S + fo;
-  // (frame rows at a 64-B pitch: whole 64-B lines per row, rx_frame_fill)
+  // (frame rows: the scratch batch is pitched at 64 B and the chunk calls below ask for whole 64-B
+  // lines per row, own_lines -- every slot, the last one included, spans round_up(FS, 64))
   const size_t n = size_t(c->n), pitch = round_up(FS, kRxFrames ? 64 : 16), slots = size_t(std::min(c->d, c->p));
   // packets per chunk: at most a kRxStageBytes stage, at least 4 chunks so copies and assembly overlap,
   // and at most 32 chunks (the chunks grow with the ring past that: see kTxMaxChunks)
@@ -1925,7 +1928,7 @@ int ugo_fec_rx_recover_host(ugo_fec* c, const uint8_t* wire, size_t slot_stride,
     if (hipStreamWaitEvent(s0, ev[b], 0) != hipSuccess) return UGO_FEC_ERR_HIP;
     // (chunk 0's wait covers the lengths' copy, earlier on the same stream; later chunks follow it on s0)
     st = rx_assemble_dev(c, base + o_stage + b * stage_bytes, slot_stride, dlens + p0, m, dpad, first_group, groups,
-                         batch, S, groups * pitch, pitch, dpres, dstats, s0, kRxFrames, base + o_rxs);
+                         batch, S, groups * pitch, pitch, dpres, dstats, s0, kRxFrames, base + o_rxs, kRxFrames);
     if (st) return st;
     if (hipEventRecord(ev[kRxStages + b], s0) != hipSuccess) return UGO_FEC_ERR_HIP;
   }

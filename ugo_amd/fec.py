@@ -386,13 +386,17 @@ class Encoder:
 
     def rx_recover_host(self, wire: np.ndarray, lens: np.ndarray, shard_size: int, groups: int,
                         first_group: int = 0, pad: Optional[bytes] = None, out: Optional[np.ndarray] = None,
-                        max_out: Optional[int] = None, present_out: Optional[np.ndarray] = None):
+                        max_out: Optional[int] = None, present_out: Optional[np.ndarray] = None,
+                        out_index: Optional[np.ndarray] = None):
         """ugo_fec_rx_recover_host: the RX path host memory to host memory.  wire =
         uint8 [npk, slot] (pinned for DMA rates), lens = uint16 [npk].  Returns
         (n, index, out, stats): n recovered data shards, the first
         min(n, max_out) of them row-compact in out[r, :shard_size] (out: uint8
         [max_out, row] with row >= shard_size, allocated if None) in ugo's
-        `recovered` order, index[r] = window group * (d+p) + row."""
+        `recovered` order, index[r] = window group * (d+p) + row (index: out_index,
+        uint32 [>= max_out], or allocated if None).  out's row stride is its second
+        dimension; only out[r, :shard_size] and index[r] for r < min(n, max_out)
+        are written."""
         npk, slot = wire.shape
         _require(wire.flags.c_contiguous and wire.itemsize == 1)
         _require(lens.flags.c_contiguous and lens.size == npk and lens.itemsize == 2)
@@ -404,7 +408,9 @@ class Encoder:
         if out is None:
             out = np.zeros((max(m, 1), (shard_size + 15) // 16 * 16), np.uint8)
         _require(out.ndim == 2 and out.flags.c_contiguous and out.shape[0] >= m and out.shape[1] >= shard_size)
-        index = np.zeros(max(m, 1), np.uint32)
+        index = np.zeros(max(m, 1), np.uint32) if out_index is None else out_index
+        _require(isinstance(index, np.ndarray) and index.flags.c_contiguous and index.itemsize == 4
+                 and index.size >= m)
         stats = np.zeros(5, np.uint32)
         padb = None if pad is None else np.frombuffer(bytes(pad), np.uint8)
         n_out = ctypes.c_size_t(0)

@@ -98,7 +98,44 @@ typedef struct ugo_pkt_segment {
  * decodes without error but has more ranges or segments than the caps gets
  * UGO_PKT_CAPACITY (the first max_* are stored); a packet the reference would
  * reject gets the reference's error whatever its size.  Returns a
- * ugo_fec_status (argument / launch errors); per-packet results are in info. */
+ * ugo_fec_status (argument / launch errors); per-packet results are in info.
+ *
+ * Input: lens[i] is an unsigned 16-bit length (a signed view of the same bits
+ * is the same length); a lens[i] above slot reads as slot.  Bytes of a slot
+ * past lens[i] are never interpreted: a reused ring slot may hold the tail of
+ * an older, longer packet there, and no output byte depends on it.  (The slot
+ * is loaded in whole 16-B chunks, so all `slot` bytes must be readable.)
+ *
+ * Output, per packet i -- the call writes info[i] and nothing outside packet
+ * i's own rows ranges[i][0 .. max_ranges) and segs[i][0 .. max_segments):
+ *
+ *   status OK         the whole 64-byte record: fields the packet does not
+ *                     carry (no SACK, no stop-waiting, a pure ACK's packet
+ *                     number) and reserved are zero; payload_off is 0, or 6
+ *                     behind a stripped typeData header; fec_flag_lo is the
+ *                     low byte of the FEC flag in framed mode when
+ *                     lens[i] >= 6, else 0.  ranges[i][0 .. n_ranges) and
+ *                     segs[i][0 .. n_segments) are written, data_off counted
+ *                     from the start of the slot; entries at or past those
+ *                     counts keep the caller's bytes.
+ *   status CAPACITY   the same, with n_ranges / n_segments clamped to the
+ *                     caps and the first max_ranges / max_segments entries
+ *                     stored (with a cap of 0 the array may be NULL, the
+ *                     count is 0 and nothing is stored).
+ *   status 1..5       status, payload_off, fec_flag_lo and reserved as above.
+ *                     The record's other fields hold what was parsed before
+ *                     the error, and the packet's own ranges / segs rows may
+ *                     hold entries parsed before it: both unspecified, as
+ *                     Conn.handlePacket drops such a packet (ugo/conn.go:
+ *                     416-419).  Nothing outside the packet's own rows is
+ *                     written.
+ *
+ * Arguments: UGO_FEC_ERR_INVALID_ARG, before any launch and with no output
+ * written, for a NULL ctx, pkts, lens or info; slot 0, not a multiple of 16
+ * or above 0xffff; pkts or pad off a 16-B boundary; flag bits other than
+ * UGO_PKT_FEC_FRAMED; max_ranges or max_segments above 0xffff; a NULL ranges
+ * (segs) with max_ranges (max_segments) > 0; pageable host memory.
+ * npackets == 0 is a no-op that returns UGO_FEC_OK. */
 int ugo_fec_packet_decode(ugo_fec* ctx, const uint8_t* pkts, size_t slot, const uint16_t* lens, size_t npackets,
                           const uint8_t* pad, unsigned flags, ugo_pkt_info* info, uint64_t* ranges,
                           size_t max_ranges, ugo_pkt_segment* segs, size_t max_segments, void* stream);

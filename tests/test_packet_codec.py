@@ -18,6 +18,7 @@ import pytest
 import torch
 
 import packet_ref as pr
+import packet_vectors as pv
 import rc4_ref
 from ugo_amd import fec
 
@@ -174,29 +175,26 @@ def _check(pk, info, ranges, segs, framed=False, max_ranges=32, max_segments=8):
         st, out = pr.decode(b[off:])
         I = info[i]
         assert I["payload_off"] == off, i
-        if st == pr.PKT_OK:
-            nr = len(out["sack"]["ranges"]) if out["sack"] else 0
-            if nr > max_ranges or len(out["segments"]) > max_segments:
-                assert I["status"] == 6, i  # UGO_PKT_CAPACITY: the first max_* are stored
-                assert I["n_ranges"] == min(nr, max_ranges) and I["n_segments"] == min(len(out["segments"]),
-                                                                                        max_segments)
-                if out["sack"] is not None:
-                    k = min(nr, max_ranges)
-                    assert [tuple(x) for x in ranges[i, :k]] == out["sack"]["ranges"][:k], i
-                continue
+        # the low byte of the FEC flag of a packet that holds a whole header, else 0
+        assert I["fec_flag_lo"] == (b[4] if framed and len(b) >= 6 else 0), i
+        assert not I["reserved"].any(), i
+        nr = len(out["sack"]["ranges"]) if st == pr.PKT_OK and out["sack"] else 0
+        ns = len(out["segments"]) if st == pr.PKT_OK else 0
+        if nr > max_ranges or ns > max_segments:
+            st = 6  # UGO_PKT_CAPACITY: decoded, the first max_* are stored and the counts clamped
+            nr, ns = min(nr, max_ranges), min(ns, max_segments)
         assert I["status"] == st, f"packet {i} {b.hex()}: status {I['status']} vs {st}"
-        if st != pr.PKT_OK:
+        if st not in (pr.PKT_OK, 6):
             continue
         assert I["flags"] == out["flags"] and I["packet_number"] == out["packet_number"], i
         assert I["stop_waiting"] == out["stop_waiting"], i
-        if out["sack"] is not None:
-            s = out["sack"]
-            assert (I["largest_acked"], I["largest_in_order"], I["delay_us"]) == \
-                (s["largest_acked"], s["largest_in_order"], s["delay_us"]), i
-            assert I["n_ranges"] == len(s["ranges"])
-            assert [tuple(x) for x in ranges[i, :len(s["ranges"])]] == s["ranges"], i
-        assert I["n_segments"] == len(out["segments"]), i
-        for j, (o, d, n, a) in enumerate(out["segments"]):
+        s = out["sack"] or {"largest_acked": 0, "largest_in_order": 0, "delay_us": 0, "ranges": []}
+        assert (I["largest_acked"], I["largest_in_order"], I["delay_us"]) == \
+            (s["largest_acked"], s["largest_in_order"], s["delay_us"]), i
+        assert I["n_ranges"] == nr, i
+        assert [tuple(x) for x in ranges[i, :nr]] == s["ranges"][:nr], i
+        assert I["n_segments"] == ns, i
+        for j, (o, d, n, a) in enumerate(out["segments"][:ns]):
             assert (segs[i, j]["offset"], segs[i, j]["data_off"], segs[i, j]["len"], segs[i, j]["avail"]) == \
                 (o, d + off, n, a), (i, j)
 
@@ -204,12 +202,16 @@ def _check(pk, info, ranges, segs, framed=False, max_ranges=32, max_segments=8):
 @pytest.mark.gpu
 def test_packet_decode_vs_oracle(gpu):
     enc = fec.New(10, 3)
-    pk = _corpus(1)
+    # the tenth byte of a uvarint and ten continuation bytes, as packet number, stop-waiting,
+    # largest acked, first block, later block and segment offset: the random corpus never gets there
+    pk = _corpus(1) + [pv.in_position(pos, pv.ENCODINGS[name]) for pos in pv.POSITIONS
+                       for name in ("ten-80x9-01", "ten-ffx9-01", "ten-80x9-02", "ten-80x9-7f", "ten-cont")]
     slot = max(len(b) for b in pk) + 15 & ~15
     info, ranges, segs = _run(enc, pk, slot)
     _check(pk, info, ranges, segs)
     codes = set(int(x) for x in info["status"])
-    assert {0, 1, 2, 4, 5} <= codes, codes  # the corpus reaches the error paths
+    assert {0, 1, 2, 3, 4, 5} <= codes, codes  # the corpus reaches the error paths
+    assert (info["status"][-30:] == 3).sum() == 18
 
 
 @pytest.mark.gpu

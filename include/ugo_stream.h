@@ -81,7 +81,9 @@
  *       spanned its offset -- is forgotten; the reference keeps its map entry
  *       for ever (and answers "duplicate" for that offset for ever).
  * Checked on the CPU against a literal restatement of push / pop / head and
- * the Read loop (tests/stream_ref.py, tests/test_stream_deliver.py).
+ * the Read loop (tests/stream_ref.py, tests/test_stream_deliver.py), and on
+ * the device at the sizes, offsets and descriptors where kernels go wrong
+ * (tests/test_stream_deliver_sizes.py).
  */
 #ifndef UGO_STREAM_H
 #define UGO_STREAM_H
@@ -142,9 +144,14 @@ void ugo_fec_stream_rx_destroy(ugo_stream_rx* rx);
  * segments at segs[i*max_segments ..], info[i].n_segments of them).  pad
  * (nullable, >= slot bytes) is XORed over segment bytes by their position in
  * the slot, exactly as the decoder applied it (the decoder never wrote the
- * plaintext back).  A segment's avail is clamped to its len and to
- * slot - data_off, n_segments to max_segments: no byte outside a packet's slot
- * is read whatever the descriptors hold.  seg_status[npackets][max_segments]
+ * plaintext back).  THE CLAMP: whatever the descriptors hold, the call uses
+ *   avail      = min(avail, len, max(0, slot - data_off))
+ *   n_segments = min(n_segments, max_segments)
+ * so the bytes of a segment are read from [data_off, data_off + avail) of its
+ * own slot (and of pad) and from nowhere else, what the clamp cuts off reads
+ * as zeros like the tail of a truncated segment, and no seg_status entry or
+ * descriptor beyond a packet's max_segments is touched.  len == 0 with avail
+ * > 0 is an empty segment.  seg_status[npackets][max_segments]
  * (uint8, device) receives a ugo_stream_status per segment entry.
  *
  * Buffers: device or pinned host memory, pageable memory is rejected;

@@ -10,7 +10,11 @@ Two restatements, both sequential Python:
   start bitmap S, with the record the device keeps.
 
 ``gen_history`` constructs histories inside the domain where the two agree
-(everything but the header's deviations (a), (b), (c)).
+(everything but the header's deviations (a), (b), (c)), from any base offset;
+both restatements can start at such a base (``RuleRx.at``, ``LiteralConn(base)``).
+``clamp_segment`` / ``packets_from_raw`` state what the call makes of raw
+descriptors, ``tile_uncovered`` builds the call that closes a history, and
+``out_of_window_rows`` the offsets of the out-of-window and aliasing table.
 """
 import numpy as np
 
@@ -43,13 +47,43 @@ class Packet:
         self.status = status
 
 
+def clamp_segment(slot, data_off, length, avail):
+    """The avail ugo_fec_stream_deliver uses (include/ugo_stream.h): never more
+    than the declared length, never past the end of the packet's slot."""
+    return min(avail, length, max(0, slot - data_off))
+
+
+def packets_from_raw(pkts, info, segs, pad=None):
+    """The Packet / Seg list the rule sees for raw descriptors, whatever they
+    hold: pkts [npk, slot] uint8 (still encrypted), info [npk] and segs [npk,
+    max_segments] structured arrays with the decoder's field names.  n_segments
+    is clamped to max_segments, avail by clamp_segment, the pad is XORed by
+    position in the slot, and what the clamp cut off reads as zeros."""
+    npk, slot = pkts.shape
+    max_segments = segs.shape[1]
+    out = []
+    for i in range(npk):
+        row = []
+        for j in range(min(int(info[i]["n_segments"]), max_segments)):
+            o, off, ln, av = (int(segs[i, j][f]) for f in ("offset", "data_off", "len", "avail"))
+            av = clamp_segment(slot, off, ln, av)
+            body = pkts[i, off:off + av] if av else np.zeros(0, np.uint8)
+            if pad is not None and av:
+                body = body ^ pad[off:off + av]
+            row.append(Seg(o, body.tobytes(), length=ln))
+        out.append(Packet(row, status=int(info[i]["status"])))
+    return out
+
+
 # --------------------------------------------------------------- the reference
 class LiteralConn:
-    def __init__(self):
+    def __init__(self, base=0):
+        """base: a connection whose first `base` bytes were delivered and read
+        in whole segments (nothing queued, one open gap from there)."""
         self.queued = {}                      # queuedFrames
-        self.read_position = 0                # segmentSorter.readPosition
-        self.gaps = [[0, MAX_BYTE_COUNT]]     # utils.ByteIntervalList
-        self.read_offset = 0                  # Conn.readOffset
+        self.read_position = base             # segmentSorter.readPosition
+        self.gaps = [[base, MAX_BYTE_COUNT]]  # utils.ByteIntervalList
+        self.read_offset = base               # Conn.readOffset
         self.read_pos_in_frame = 0
         self.eof = False
         self.err = NONE
@@ -189,8 +223,36 @@ class RuleRx:
         self.accepted = self.duplicate = self.out_of_window = self.skipped_packets = 0
         self.contested = 0   # not device state: what the ordered pass must have seen in the last call
 
+    @classmethod
+    def at(cls, cap, read_pos, sentinel=0, window=None, **counters):
+        """A connection that has delivered and read [0, read_pos) in whole
+        segments: nothing covered, nothing queued, hi = read_pos.  window: the
+        ring's content (default: the sentinel); counters: accepted, duplicate,
+        out_of_window, skipped_packets so far."""
+        r = cls(cap, sentinel)
+        r.read_pos = r.hi = read_pos
+        if window is not None:
+            r.W[:] = window
+        for k, v in counters.items():
+            assert k in ("accepted", "duplicate", "out_of_window", "skipped_packets"), k
+            setattr(r, k, v)
+        return r
+
     def _idx(self, lo, hi):
         return np.arange(lo, hi) & (self.cap - 1)
+
+    def _ring(self, arr, lo, hi):
+        """arr over stream positions [lo, hi) (hi - lo <= cap), as a copy."""
+        a, n = lo & (self.cap - 1), hi - lo
+        if a + n <= self.cap:
+            return arr[a:a + n].copy()
+        return np.concatenate([arr[a:], arr[:a + n - self.cap]])
+
+    def _ring_fill(self, arr, lo, hi, value):
+        a, n = lo & (self.cap - 1), hi - lo
+        arr[a:min(a + n, self.cap)] = value
+        if a + n > self.cap:
+            arr[:a + n - self.cap] = value
 
     def _covered(self, o, e):
         """(any covered, all covered) over [o, e)."""
@@ -225,7 +287,40 @@ class RuleRx:
             return DUPLICATE
         return OVERLAP
 
+    def _claimers(self, packets):
+        """(ring indices claimed, partly covered) per claimer of the batch, in
+        arrival order; see _contested_count_sets."""
+        rp, cap = self.read_pos, self.cap
+        for p in packets:
+            if p.status != 0:
+                continue
+            for s in p.segs:
+                o, e = s.offset, s.offset + s.length
+                inwin = rp <= o < rp + cap
+                if (inwin and self.S[o & (cap - 1)]) or (self.head_valid and o == self.head_off):
+                    continue
+                if s.length == 0:
+                    if inwin:
+                        yield np.array([o & (cap - 1)]), False
+                    continue
+                if e > rp + cap or e <= rp:
+                    continue
+                lo = max(o, rp)
+                ix = self._idx(lo, e)
+                ux = ix[~self.C[ix]]
+                if len(ux):
+                    yield ux, bool(o < rp or len(ux) != e - lo)
+
     def _contested_count(self, packets):
+        """_contested_count_sets over two byte maps of the ring (claimed once,
+        claimed twice) instead of Python sets: the same count, at any size."""
+        once, twice = np.zeros(self.cap, bool), np.zeros(self.cap, bool)
+        for ux, _ in self._claimers(packets):
+            twice[ux] |= once[ux]
+            once[ux] = True
+        return sum(1 for ux, partly in self._claimers(packets) if partly or twice[ux].any())
+
+    def _contested_count_sets(self, packets):
         """Segments the parallel passes cannot decide (stream_kernels.hip): the
         claimers -- segments with an uncovered byte that are not duplicates by
         the state before the call, and in-window empty segments -- whose claims
@@ -305,7 +400,7 @@ class RuleRx:
 
     def _summary(self):
         rp, cap = self.read_pos, self.cap
-        cov = self.C[self._idx(rp, self.hi)] if self.hi > rp else np.zeros(0, bool)
+        cov = self._ring(self.C, rp, self.hi) if self.hi > rp else np.zeros(0, bool)
         unc = ~cov
         runs = int(unc[0]) + int(np.count_nonzero(unc[1:] & cov[:-1])) if len(unc) else 0
         self.ngaps = runs + 1
@@ -318,19 +413,18 @@ class RuleRx:
     def read(self, n):
         rp, cap = self.read_pos, self.cap
         m = min(n, self.readable)
-        ix = self._idx(rp, rp + m)
-        data = self.W[ix].tobytes()
+        data = self._ring(self.W, rp, rp + m).tobytes()
         eof = m == self.readable and self.eof
         if m > 0:
             new = rp + m
             partly = m < self.readable and not self.S[new & (cap - 1)]
-            starts = np.flatnonzero(self.S[ix])
+            starts = np.flatnonzero(self._ring(self.S, rp, new))
             if not partly:
                 self.head_valid, self.head_off = False, 0
             elif len(starts):
                 self.head_valid, self.head_off = True, rp + int(starts[-1])
-            self.C[ix] = False
-            self.S[ix] = False
+            self._ring_fill(self.C, rp, new, False)
+            self._ring_fill(self.S, rp, new, False)
             self.read_pos = new
             self.readable -= m
         return data, eof
@@ -344,7 +438,8 @@ class RuleRx:
 
 
 # ------------------------------------------------------------------- histories
-def gen_history(rng, total_max=3000, seg_max=64, calls=(3, 6), in_batch_dups=False, max_packets=256):
+def gen_history(rng, total_max=3000, seg_max=64, calls=(3, 6), in_batch_dups=False, max_packets=256,
+                base=0, total=None, forced=(), fin=True):
     """A history inside the domain: ('deliver', [Packet]) and ('read', n) steps.
 
     The stream [0, total) is tiled into segments.  A tile may be sent whole, or
@@ -353,18 +448,32 @@ def gen_history(rng, total_max=3000, seg_max=64, calls=(3, 6), in_batch_dups=Fal
     same offset and an equal or shorter length.  Tiles go out nearly in order
     (shuffled within runs of 8, so far fewer than 50 gaps ever exist), one
     empty segment closes the stream, reads of random sizes sit between the
-    calls.  in_batch_dups: some packets are repeated inside their batch."""
-    total = int(rng.integers(200, total_max))
+    calls.  in_batch_dups: some packets are repeated inside their batch.
+
+    base: the stream is [base, base + total) of a connection that starts there
+    (RuleRx.at, LiteralConn(base)); data[k] is stream byte base + k.  total: a
+    given length.  forced: (start, length) tiles relative to base that are sent
+    whole, so that a segment ends, starts or lies across a chosen offset.
+    fin=False: no empty segment, the connection stays open."""
+    total = int(rng.integers(200, total_max)) if total is None else total
     data = rng.integers(0, 256, total, dtype=np.uint8).tobytes()
+    forced = dict(forced)
     sends = []
     o = 0
     while o < total:
-        ln = int(min(total - o, rng.integers(1, seg_max + 1)))
+        if o in forced:
+            ln = forced[o]
+            assert o + ln <= total and not any(o < f < o + ln for f in forced)
+            sends.append([Seg(base + o, data[o:o + ln])])
+            o += ln
+            continue
+        stop = min([total] + [f for f in forced if f > o])
+        ln = int(min(stop - o, rng.integers(1, seg_max + 1)))
         if ln >= 2 and rng.random() < 0.25:
             short = int(rng.integers(1, ln))
-            sends.append([Seg(o, data[o:o + short]), Seg(o + short, data[o + short:o + ln])])
+            sends.append([Seg(base + o, data[o:o + short]), Seg(base + o + short, data[o + short:o + ln])])
         else:
-            sends.append([Seg(o, data[o:o + ln])])
+            sends.append([Seg(base + o, data[o:o + ln])])
         o += ln
     for k in range(0, len(sends), 8):
         run = sends[k:k + 8]
@@ -373,7 +482,8 @@ def gen_history(rng, total_max=3000, seg_max=64, calls=(3, 6), in_batch_dups=Fal
     order = []
     for grp in sends:
         order.extend(grp)
-    order.append(Seg(total))
+    if fin:
+        order.append(Seg(base + total))
     # retransmissions: later than the original, same offset, equal or shorter
     k = 0
     while k < len(order):
@@ -407,3 +517,42 @@ def gen_history(rng, total_max=3000, seg_max=64, calls=(3, 6), in_batch_dups=Fal
     steps.append(("read", total + 10))
     steps.append(("read", 5))
     return steps, data
+
+
+def shift_history(steps, k):
+    """The same history k bytes further along the stream."""
+    return [(op, [Packet([Seg(s.offset + k, s.data, s.length) for s in p.segs], p.status) for p in arg])
+            if op == "deliver" else (op, arg) for op, arg in steps]
+
+
+def tile_uncovered(rule, rng, seg_max, lo=None, hi=None):
+    """Fresh one-segment packets that tile every uncovered byte of [lo, hi)
+    (default: the whole window [read_pos, read_pos + cap)) of `rule`, runs in
+    ascending order, segments of 1..seg_max bytes."""
+    lo = rule.read_pos if lo is None else lo
+    hi = rule.read_pos + rule.cap if hi is None else hi
+    unc = np.concatenate([[False], ~rule._ring(rule.C, lo, hi), [False]])
+    edges = np.flatnonzero(unc[1:] != unc[:-1])
+    packets = []
+    for a, b in zip(edges[0::2], edges[1::2]):
+        o, e = lo + int(a), lo + int(b)
+        while o < e:
+            n = int(min(e - o, rng.integers(max(1, seg_max // 2), seg_max + 1)))
+            packets.append(Packet([Seg(o, rng.integers(0, 256, n, dtype=np.uint8).tobytes())]))
+            o += n
+    return packets
+
+
+def out_of_window_rows(read_pos, cap, live, length):
+    """The offsets of the out-of-window and aliasing table for one segment
+    length: (name, offset) in a fixed order.  live: positions x that hold a
+    start or a coverage bit.  Offsets that 64 bits cannot hold are left out."""
+    rows = []
+    for x in live:
+        rows += [(f"x{x}+cap", x + cap), (f"x{x}+2cap", x + 2 * cap), (f"x{x}+2^32", x + (1 << 32))]
+        if 0 <= x - cap < read_pos:
+            rows.append((f"x{x}-cap", x - cap))
+    rows += [("2^63", 1 << 63), ("2^64-1", (1 << 64) - 1), ("2^64-len", (1 << 64) - length),
+             ("2^64-len+1", (1 << 64) - length + 1), ("fits", read_pos + cap - length),
+             ("fits+1", read_pos + cap - length + 1)]
+    return [(n, o) for n, o in rows if o < (1 << 64)]

@@ -21,11 +21,10 @@ import pytest
 import torch
 
 import stream_ref as sr
+from stream_harness import SENTINEL, Harness, enc, pad_bytes  # noqa: F401  (fixtures)
+from stream_harness import rand_bytes as _bytes
 from stream_ref import Packet, Seg
 from ugo_amd import fec
-
-KEY = b"1234567890123456"  # ugo/listener.go:92, ugo/dial.go:132
-SENTINEL = 0xA5
 
 
 # ------------------------------------------------------------------ CPU tests
@@ -144,118 +143,6 @@ def test_python_argument_checks():
 
 
 # ------------------------------------------------------------------ GPU tests
-@pytest.fixture(scope="module")
-def enc(gpu):
-    e = fec.New(10, 3, device=0)
-    yield e
-    e.close()
-
-
-@pytest.fixture(scope="module")
-def pad_bytes():
-    return np.frombuffer(fec.rc4_keystream(KEY, 1488), np.uint8).copy()
-
-
-def build_batch(packets, slot, max_segments, pad, data_off=None, seed=0):
-    """The decoder's view of `packets`: (pkts [npk, slot] still encrypted, info,
-    segs).  Segment j of packet i sits at data_off(i, j) -- default: packed
-    behind a few header bytes -- and is XORed with pad by its position."""
-    rng = np.random.default_rng(seed)
-    npk = len(packets)
-    pkts = rng.integers(0, 256, (npk, slot), dtype=np.uint8)   # header bytes and slack: noise
-    info = np.zeros(npk, fec.PKT_INFO_DTYPE)
-    segs = np.zeros((npk, max_segments), fec.PKT_SEGMENT_DTYPE)
-    for i, p in enumerate(packets):
-        info[i]["status"] = p.status
-        info[i]["n_segments"] = len(p.segs)
-        cur = int(rng.integers(1, 24))
-        for j, s in enumerate(p.segs):
-            off = cur + int(rng.integers(3, 12)) if data_off is None else data_off(i, j)
-            av = len(s.data)
-            assert off + av <= slot, (off, av, slot)
-            body = np.frombuffer(s.data, np.uint8)
-            pkts[i, off:off + av] = body ^ pad[off:off + av] if pad is not None else body
-            segs[i, j] = (s.offset, off, s.length, av)
-            cur = off + av
-    return pkts, info, segs
-
-
-class Harness:
-    """One connection on the device beside the rule (and, inside the common
-    domain, the literal reference); every step is compared."""
-
-    def __init__(self, enc, cap, slot=256, max_segments=4, pad=None, literal=False):
-        self.rx = fec.StreamRx(enc, cap)
-        self.rule = sr.RuleRx(cap, SENTINEL)
-        self.lit = sr.LiteralConn() if literal else None
-        self.cap, self.slot, self.max_segments = cap, slot, max_segments
-        self.pad = pad
-        self.dpad = None if pad is None else torch.from_numpy(pad).cuda()
-        st = self.rx.state()
-        assert st["ngaps"] == 1 and st["read_pos"] == 0 and st["err"] == 0
-        assert not self.rx.window().any().item()               # create zeroes the window
-        self.rx.window().fill_(SENTINEL)
-        self.ordered = 0
-        self.calls = 0
-
-    def close(self):
-        self.rx.close()
-
-    def check(self):
-        st = self.rx.state()
-        want = self.rule.record()
-        got = {k: int(st[k]) for k in want}
-        assert got == want
-        assert int(st["ordered_segments"]) == self.ordered
-        win = self.rx.window().cpu().numpy()
-        bad = np.flatnonzero(win != self.rule.W)
-        assert bad.size == 0, f"window differs at {bad[:8]} (of {bad.size})"
-
-    def deliver(self, packets, data_off=None, ordered="count", raw=None):
-        """ordered: "count" -- ordered_segments must grow by exactly the rule's
-        contested count; an int -- by exactly that; None -- it is read back."""
-        self.calls += 1
-        pkts, info, segs = raw if raw is not None else build_batch(packets, self.slot, self.max_segments, self.pad,
-                                                                   data_off, seed=self.calls)
-        dp = torch.from_numpy(pkts).cuda()
-        di = torch.from_numpy(info.view(np.uint8).reshape(len(packets), 64)).cuda()
-        ds = torch.from_numpy(segs.view(np.uint8).reshape(len(packets), self.max_segments, 16)).cuda()
-        status = torch.full((len(packets), self.max_segments), 0x77, dtype=torch.uint8, device="cuda")
-        self.rx.deliver(dp, di, ds, pad=self.dpad, out=status)
-        want = self.rule.deliver(packets, count_contested=ordered == "count")
-        got = status.cpu().numpy()
-        exp = np.zeros_like(got)
-        for i, row in enumerate(want):
-            exp[i, :len(row)] = row
-        assert np.array_equal(got, exp), (np.argwhere(got != exp)[:8], got[got != exp][:8], exp[got != exp][:8])
-        if ordered == "count":
-            self.ordered += self.rule.contested
-        elif ordered is None:
-            self.ordered = int(self.rx.state()["ordered_segments"])
-        else:
-            self.ordered += ordered
-        self.check()
-        if self.lit is not None:
-            assert self.lit.deliver(packets) == want
-        return got
-
-    def read(self, n, discard=False):
-        buf, n_read, eof = self.rx.read(n, discard=discard)
-        data, want_eof = self.rule.read(n)
-        m = int(n_read.item())
-        assert m == len(data) and bool(eof.item()) == want_eof
-        if not discard:
-            assert buf[:m].cpu().numpy().tobytes() == data
-        self.check()
-        if self.lit is not None:
-            assert self.lit.read(n) == (data, want_eof)
-        return data, want_eof
-
-
-def _bytes(rng, n):
-    return rng.integers(0, 256, n, dtype=np.uint8).tobytes()
-
-
 @pytest.mark.gpu
 def test_argument_checks_against_a_context(enc):
     lib = fec.load_library()
@@ -469,6 +356,7 @@ def test_contested_batches(enc, pad_bytes):
     got = h.deliver([Packet([Seg(700, _bytes(rng, 20))]), Packet([Seg(710)])], ordered=2)
     assert got[:, 0].tolist() == [1, 1]
     assert h.ordered == 15
+    h.finish()                                                     # no claim or contested bit stayed behind
     h.close()
 
 
@@ -588,6 +476,7 @@ def test_random_histories(enc, pad_bytes):
                 got += h.read(arg)[0]
         assert bytes(got) == data and h.rule.eof, seed
         ordered += h.ordered
+        h.finish(seed)                               # the ring holds no stale bit of the history
         streams += 1
         h.close()
     assert streams == 200 and ordered > 200          # the ordered pass had its share
@@ -616,7 +505,7 @@ def test_chain_encode_decode_deliver_read(enc, pad_bytes, framed):
     di = torch.from_numpy(info.view(np.uint8).reshape(npk, 64)).cuda()
     ds = torch.from_numpy(segs.view(np.uint8).reshape(npk, max_segments, 16)).cuda()
     ranges = torch.zeros((npk, 1, 2), dtype=torch.int64, device="cuda")
-    dpad = torch.from_numpy(pad_bytes).cuda()
+    dpad = torch.from_numpy(pad_bytes[:slot]).cuda()
     wire, wire_lens, status = enc.packet_encode(di, ranges, ds, stream, slot, pad=None if framed else dpad,
                                                 framed=framed)
     assert not status.any().item()

@@ -780,10 +780,11 @@ class StreamRx:
             segs.data_ptr(), max_segments, npk, out.data_ptr(), _stream_handle(stream)))
         return out
 
-    def read(self, n: int, out=None, discard: bool = False, stream=None):
+    def read(self, n: int, out=None, discard: bool = False, stream=None, n_read=None, eof=None):
         """ugo_fec_stream_read, Conn.Read(p[:n]) that never waits.  Returns CUDA
         tensors (buf uint8 [n] -- None with discard --, n_read int64 [1], eof uint8
-        [1]): buf[:n_read] holds the bytes.  Nothing is synchronised."""
+        [1]): buf[:n_read] holds the bytes.  out (any alignment), n_read and eof
+        may be given, in device or pinned host memory.  Nothing is synchronised."""
         _require(n >= 0)
         dev = torch.device("cuda", self.device)
         if discard:
@@ -792,8 +793,11 @@ class StreamRx:
             out = torch.empty(max(n, 1), dtype=torch.uint8, device=dev)
         if out is not None:
             _require(out.is_contiguous() and out.element_size() == 1 and out.numel() >= n)
-        n_read = torch.zeros(1, dtype=torch.int64, device=dev)
-        eof = torch.zeros(1, dtype=torch.uint8, device=dev)
+        if n_read is None:
+            n_read = torch.zeros(1, dtype=torch.int64, device=dev)
+        if eof is None:
+            eof = torch.zeros(1, dtype=torch.uint8, device=dev)
+        _require(n_read.numel() == 1 and n_read.element_size() == 8 and eof.numel() == 1 and eof.element_size() == 1)
         _raise(load_library().ugo_fec_stream_read(self._h, None if out is None else out.data_ptr(), n,
                                                   n_read.data_ptr(), eof.data_ptr(), _stream_handle(stream)))
         return out, n_read, eof

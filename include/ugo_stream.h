@@ -178,6 +178,70 @@ int ugo_fec_stream_rx_state(ugo_stream_rx* rx, ugo_stream_rx_state* host_out);
  * readable)). */
 int ugo_fec_stream_rx_window(ugo_stream_rx* rx, uint8_t** window_dev, size_t* window_bytes);
 
+/* ---- Receive-window sets: many connections per call ----------------------
+ *
+ * Added within ABI version 9 (ugo_fec_abi_version() still returns 9): the
+ * presence of the ugo_fec_stream_set_* symbols is the feature test.
+ *
+ * ugo uses one fixed RC4 key, so a decoded batch holds packets of any number
+ * of connections, interleaved as the listener received them.  A set is an
+ * ordered list of existing receive windows (their sizes may differ); packet i
+ * of a batch belongs to member conn_of[i].  The set does not own its members:
+ * destroy the set first, then the members.  Members cannot be added to or
+ * removed from a live set; destroy it and create another.  create uploads one
+ * table entry per member (window, four bitmaps, record, cap), once, so the
+ * per-call entry points make no host-to-device copy and no host
+ * synchronisation.  create returns UGO_FEC_ERR_INVALID_ARG for a NULL
+ * argument, nconn == 0 or nconn > 2^20, a NULL member, a member of another
+ * context, or the same ugo_stream_rx listed twice.
+ *
+ * Calls on a member through the single entry points and through a set may be
+ * mixed; the caller orders them, as it orders the calls on one rx.
+ * ugo_fec_stream_rx_state and ugo_fec_stream_rx_window on a member reflect
+ * the set's calls.  The launches report as kernel classes
+ * UGO_FEC_KERNEL_STREAM_DELIVER and UGO_FEC_KERNEL_STREAM_READ.  Checked on
+ * the device against one rule per member, where blocks mix connections
+ * (tests/stream_set_harness.py, tests/test_stream_set.py). */
+#define UGO_STREAM_NO_CONN 0xffffffffu
+
+typedef struct ugo_stream_rx_set ugo_stream_rx_set;
+
+int ugo_fec_stream_set_create(ugo_fec* ctx, ugo_stream_rx* const* rxs, size_t nconn, ugo_stream_rx_set** out);
+void ugo_fec_stream_set_destroy(ugo_stream_rx_set* set);
+
+/* ugo_fec_stream_deliver with one more operand: conn_of[npackets] (uint32,
+ * device or pinned host memory), the index into the set of the connection
+ * packet i belongs to.  For every member c the call has exactly the effect of
+ * ugo_fec_stream_deliver on member c with the subsequence of packets
+ * {i : conn_of[i] == c}, in batch order -- statuses, record, window, bitmaps --
+ * except that err_packet is the packet's index in this call's batch and
+ * seg_status rows are indexed by batch packet index.  A member with no packet
+ * in the call keeps its record bit for bit.  A packet whose conn_of[i] is
+ * UGO_STREAM_NO_CONN or any other value >= nconn belongs to no connection (the
+ * clamp policy: a lying descriptor is clamped, never followed): its seg_status
+ * row is all zero over max_segments and it is counted in no record.  Errors
+ * stay per connection: a fatal overlap stops its own connection only, and a
+ * member that is already in error gets status 0 for all its packets and
+ * nothing of it is touched.  Argument checks, alignment rules, npackets == 0
+ * and stream ordering as for ugo_fec_stream_deliver. */
+int ugo_fec_stream_set_deliver(ugo_stream_rx_set* set, const uint8_t* pkts, size_t slot, const uint8_t* pad,
+                               const ugo_pkt_info* info, const ugo_pkt_segment* segs, size_t max_segments,
+                               size_t npackets, const uint32_t* conn_of, uint8_t* seg_status, void* stream);
+
+/* Conn.Read for every member in one launch; n, dst_off, n_read and eof are
+ * arrays of nconn elements in device or pinned host memory.  Per member c the
+ * effect is ugo_fec_stream_read(member c, dst + dst_off[c], n[c], &n_read[c],
+ * &eof[c]), except that n[c] == 0 skips the member: its record is untouched,
+ * n_read[c] = 0, eof[c] = 0.  dst NULL discards for all members (dst_off may
+ * then be NULL); eof may be NULL.  The caller keeps the destination ranges
+ * disjoint; the call does not check them. */
+int ugo_fec_stream_set_read(ugo_stream_rx_set* set, uint8_t* dst, const uint64_t* dst_off, const uint64_t* n,
+                            uint64_t* n_read, uint8_t* eof, void* stream);
+
+/* The nconn records, in set order, after synchronising the stream of the last
+ * call on the set: gathered on the device and copied out in one transfer. */
+int ugo_fec_stream_set_state(ugo_stream_rx_set* set, ugo_stream_rx_state* host_out /* [nconn] */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -59,6 +59,7 @@
 
 #include "launch.hpp"
 #include "stream_kernels.hpp"
+#include "stream_device.hpp"
 
 namespace ugo {
 namespace kern {
@@ -72,75 +73,9 @@ void stream_record_init(StreamRecord* r) {
 
 namespace {
 
-typedef unsigned long long u64;
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x4u __attribute__((ext_vector_type(4), aligned(1)));
-
-constexpr uint32_t kGroupLanes = 16;  // lanes per packet in classify / resolve
-constexpr uint32_t kGroupsPerBlock = 256 / kGroupLanes;
-constexpr uint32_t kCopyLanes = 32;        // lanes per packet in the copy
-constexpr uint32_t kCopyPacketsPerBlock = 64;
-constexpr uint32_t kScanBlocks = 1024;
-constexpr uint32_t kOrderedThreads = 1024;
-constexpr uint32_t kEndShards = 64;
-static_assert(kEndShards == sizeof(StreamRecord::claim_end) / sizeof(unsigned long long), "one word per shard");
-
-// statuses between the kernels of one call (never left in seg_status)
-enum : uint32_t {
-  kNone = UGO_STREAM_NONE,
-  kAccepted = UGO_STREAM_ACCEPTED,
-  kDuplicate = UGO_STREAM_DUPLICATE,
-  kOutOfWindow = UGO_STREAM_OUT_OF_WINDOW,
-  kOverlap = UGO_STREAM_OVERLAP,
-  kPartial = 0xFC,    // partly covered before the call: always ordered
-  kFinCand = 0xFD,    // empty segment that claimed its offset
-  kCand = 0xFE,       // wholly uncovered before the call, claimed its range
-  kContested = 0xFF,  // for the ordered pass
-};
-
-struct Seg {
-  u64 o;
-  uint32_t data_off, len, avail;
-};
-
-__device__ __forceinline__ Seg to_seg(const StreamArgs& a, const ugo_pkt_segment& s) {
-  Seg r;
-  r.o = s.offset;
-  r.data_off = s.data_off;
-  r.len = s.len;
-  uint32_t av = s.avail < s.len ? s.avail : s.len;
-  const u64 room = s.data_off < a.slot ? a.slot - s.data_off : 0;  // never read past the slot
-  r.avail = av < room ? av : static_cast<uint32_t>(room);
-  return r;
-}
-__device__ __forceinline__ Seg load_seg(const StreamArgs& a, u64 idx) { return to_seg(a, a.segs[idx]); }
-
-// The word that holds stream positions [p, p + 64) (p a multiple of 64): the
-// bits of [max(p, lo), min(p + 64, e)).  lo < p + 64 and e > p.
-__device__ __forceinline__ u64 range_mask(u64 p, u64 lo, u64 e) {
-  const u64 a = lo > p ? lo - p : 0;
-  const u64 b = e - p;
-  const u64 hi = b >= 64 ? ~0ull : ((1ull << b) - 1ull);
-  return hi & ~((1ull << a) - 1ull);
-}
-__device__ __forceinline__ u64 widx(u64 p, u64 cap) { return (p & (cap - 1)) >> 6; }
-__device__ __forceinline__ u64 words_of(u64 lo, u64 e) { return (e - (lo & ~63ull) + 63) >> 6; }
-__device__ __forceinline__ u64 aload(const u64* p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// "any lane of my 16-lane group": the groups of a wave branch apart, but the
-// lanes of one group never do, so the group's ballot bits are all its own.
-__device__ __forceinline__ bool group_any(bool v) {
-  const u64 b = __ballot(v);
-  const uint32_t g = (threadIdx.x & 63u) / kGroupLanes;
-  return ((b >> (g * kGroupLanes)) & ((1u << kGroupLanes) - 1u)) != 0;
-}
-
-__device__ __forceinline__ uint32_t nseg_of(const StreamArgs& a, u64 i) {
-  const uint32_t n = a.info[i].n_segments;
-  return n < a.max_segments ? n : a.max_segments;
-}
+// The statuses between the kernels, the clamped segment, the bitmap word
+// arithmetic, ordered_one and copy_segment live in stream_device.hpp, shared
+// with the set kernels (stream_set_kernels.hip).
 
 // ------------------------------------------------------------ classify + claim
 __global__ __launch_bounds__(256) void k_stream_classify(StreamArgs a) {
@@ -289,64 +224,6 @@ __global__ __launch_bounds__(256) void k_stream_apply(StreamArgs a) {
 }
 
 // --------------------------------------------------------------- ordered pass
-// One contested segment, by the 64 lanes of wave 0: steps 2-7 of the rule
-// against the bitmaps as they are now.  Reads and writes go to L2 (atomics), and
-// a fence ends each segment, so the next one sees this one's bits.
-__device__ bool ordered_one(const StreamArgs& a, u64 idx, uint32_t lane, u64 rp, u64 head, bool hv) {
-  const u64 cap = a.cap;
-  const Seg s = load_seg(a, idx);
-  const bool indom = s.o >= rp && s.o - rp < cap;
-  u64* sw = a.S + widx(s.o, cap);
-  const u64 sbit = 1ull << (s.o & 63);
-  uint32_t res;
-  if ((hv && s.o == head) || (indom && (aload(sw) & sbit))) {
-    res = kDuplicate;
-  } else if (s.len == 0) {
-    if (lane == 0) atomicOr(sw, sbit);
-    res = kAccepted;
-  } else {
-    const u64 e = s.o + s.len, lo = s.o > rp ? s.o : rp;
-    const u64 p0 = lo & ~63ull, nw = words_of(lo, e);
-    bool anyc = s.o < rp, anyu = false;
-    for (u64 k = lane; k < nw; k += 64) {
-      const u64 p = p0 + 64 * k, m = range_mask(p, lo, e), w = aload(a.C + widx(p, cap));
-      anyc |= (w & m) != 0;
-      anyu |= (~w & m) != 0;
-    }
-    anyc = __any(anyc);
-    anyu = __any(anyu);
-    if (!anyc) {
-      for (u64 k = lane; k < nw; k += 64) {
-        const u64 p = p0 + 64 * k;
-        atomicOr(a.C + widx(p, cap), range_mask(p, lo, e));
-      }
-      if (lane == 0) atomicOr(sw, sbit);
-      res = kAccepted;
-    } else if (!anyu) {
-      res = kDuplicate;
-    } else {
-      res = kOverlap;
-      if (lane == 0) {
-        a.rec->pub.err = UGO_STREAM_OVERLAP;
-        a.rec->pub.err_packet = idx / a.max_segments;
-        a.rec->pub.err_segment = static_cast<uint32_t>(idx % a.max_segments);
-        a.rec->fatal_idx = idx;
-      }
-    }
-  }
-  // its contested bits have served (k_stream_resolve read them)
-  if (s.len == 0) {
-    if (lane == 0) *(a.cont + widx(s.o, cap)) = 0;
-  } else {
-    const u64 e = s.o + s.len, lo = s.o > rp ? s.o : rp;
-    const u64 p0 = lo & ~63ull, nw = words_of(lo, e);
-    for (u64 k = lane; k < nw; k += 64) a.cont[widx(p0 + 64 * k, cap)] = 0;
-  }
-  if (lane == 0) a.seg_status[idx] = static_cast<uint8_t>(res);
-  __threadfence();
-  return res == kOverlap;
-}
-
 __global__ __launch_bounds__(kOrderedThreads) void k_stream_ordered(StreamArgs a) {
   StreamRecord& R = *a.rec;
   const uint32_t todo = R.n_contested;
@@ -403,57 +280,6 @@ __global__ __launch_bounds__(kOrderedThreads) void k_stream_ordered(StreamArgs a
 }
 
 // ------------------------------------------------ counters, undo, clear, copy
-__device__ __forceinline__ u32x4 ldu16(const uint8_t* p) { return *reinterpret_cast<const u32x4u*>(p); }
-
-__device__ __forceinline__ uint32_t seg_byte(const uint8_t* src, const uint8_t* padp, uint32_t k, uint32_t avail) {
-  if (k >= avail) return 0u;
-  uint32_t v = src[k];
-  if (padp) v ^= padp[k];
-  return v;
-}
-
-// The accepted segment's bytes into the window, by kCopyLanes lanes.  Whole
-// 16-B chunks of the stream (they are whole chunks of the window too, and none
-// straddles the wrap): one unaligned 16-B load, the pad XOR, one aligned
-// nontemporal 16-B store.  The up-to-15 bytes on either side: byte stores, one
-// per lane.  No byte outside [o, o + len) is written.
-__device__ __forceinline__ void copy_segment(const StreamArgs& a, u64 i, const Seg& s, uint32_t hl) {
-  const uint8_t* src = a.pkts + i * a.slot + s.data_off;
-  const uint8_t* padp = a.pad ? a.pad + s.data_off : nullptr;
-  const u64 o = s.o, e = s.o + s.len, capm = a.cap - 1;
-  const u64 c0 = (o + 15) >> 4, c1 = e >> 4;  // whole chunks [c0, c1)
-  for (u64 c = c0 + hl; c < c1; c += 4ull * kCopyLanes) {
-    u32x4 v[4];
-#pragma unroll
-    for (uint32_t q = 0; q < 4; ++q) {
-      const u64 cc = c + q * kCopyLanes;
-      if (cc < c1) {
-        const uint32_t k = static_cast<uint32_t>(16 * cc - o);
-        if (k + 16u <= s.avail) {
-          v[q] = ldu16(src + k);
-          if (padp) v[q] ^= ldu16(padp + k);
-        } else {  // the chunk where a truncated segment ends, and its zero tail
-          uint32_t w[4] = {0u, 0u, 0u, 0u};
-          if (k < s.avail)
-#pragma unroll
-            for (uint32_t b = 0; b < 16; ++b) w[b >> 2] |= seg_byte(src, padp, k + b, s.avail) << (8u * (b & 3u));
-          v[q] = u32x4{w[0], w[1], w[2], w[3]};
-        }
-      }
-    }
-#pragma unroll
-    for (uint32_t q = 0; q < 4; ++q) {
-      const u64 cc = c + q * kCopyLanes;
-      if (cc < c1) __builtin_nontemporal_store(v[q], reinterpret_cast<u32x4*>(a.win + ((16 * cc) & capm)));
-    }
-  }
-  const u64 head_end = e < 16 * c0 ? e : 16 * c0;                   // head bytes [o, head_end)
-  const u64 tail_start = 16 * c1 > head_end ? 16 * c1 : head_end;  // tail bytes [tail_start, e)
-  const u64 x = hl < 16 ? o + hl : tail_start + (hl - 16);
-  if (hl < 16 ? x < head_end : x < e)
-    a.win[x & capm] = static_cast<uint8_t>(seg_byte(src, padp, static_cast<uint32_t>(x - o), s.avail));
-}
-
 __global__ __launch_bounds__(256) void k_stream_copy(StreamArgs a) {
   StreamRecord& R = *a.rec;
   if (R.inert != 0) return;

@@ -23,7 +23,7 @@ struct StreamRecord {
   uint32_t accepted_data;        // this call accepted a non-empty segment
   uint32_t inert;                // err was set before this call: nothing is processed
   uint32_t ticket;               // read: blocks that have finished
-  uint32_t pad_;
+  uint32_t touched;              // set calls only: a packet of this call belongs here (idle: 0)
 };
 
 void stream_record_init(StreamRecord* host);

@@ -31,6 +31,7 @@
 #include "tx_kernels.hpp"
 #include "pkt_kernels.hpp"
 #include "stream_kernels.hpp"
+#include "stream_set_kernels.hpp"
 
 namespace {
 
@@ -2221,7 +2222,28 @@ struct ugo_stream_rx {
   unsigned long long* bits = nullptr;  // C | S | claim | contested, cap / 64 words each
   ugo::kern::StreamRecord* rec = nullptr;
   hipStream_t last = nullptr;  // the stream of the last deliver / read
+  std::vector<ugo_stream_rx_set*> sets;  // the live sets it is a member of: their calls are its calls
 };
+
+struct ugo_stream_rx_set {
+  ugo_fec* ctx = nullptr;
+  std::vector<ugo_stream_rx*> members;
+  ugo::kern::StreamSetEntry* table = nullptr;  // device, [nconn], uploaded once
+  ugo_stream_rx_state* gathered = nullptr;     // device, [nconn], for ugo_fec_stream_set_state
+  uint32_t wblocks = 1, rblocks = 1;           // per-connection grid sizes, from the largest member window
+  hipStream_t last = nullptr;                  // the stream of the last call on the set
+  bool used = false;
+};
+
+namespace {
+// the calls made on rx through the sets it belongs to
+hipError_t stream_rx_sync_sets(ugo_stream_rx* rx) {
+  hipError_t e = hipSuccess;
+  for (ugo_stream_rx_set* set : rx->sets)
+    if (set->used && e == hipSuccess) e = hipStreamSynchronize(set->last);
+  return e;
+}
+}  // namespace
 
 int ugo_fec_stream_rx_create(ugo_fec* c, size_t window_bytes, ugo_stream_rx** out) {
   static_assert(sizeof(ugo_stream_rx_state) == 96, "ugo_stream_rx_state is 96 bytes");
@@ -2259,6 +2281,7 @@ void ugo_fec_stream_rx_destroy(ugo_stream_rx* rx) {
   {
     DeviceGuard g(rx->ctx->device);
     if (rx->last) (void)hipStreamSynchronize(rx->last);
+    (void)stream_rx_sync_sets(rx);
     (void)hipFree(rx->win);
     (void)hipFree(rx->bits);
     (void)hipFree(rx->rec);
@@ -2331,7 +2354,7 @@ int ugo_fec_stream_rx_state(ugo_stream_rx* rx, ugo_stream_rx_state* host_out) {
   if (!rx || !host_out) return UGO_FEC_ERR_INVALID_ARG;
   DeviceGuard g(rx->ctx->device);
   if (!g.ok) return UGO_FEC_ERR_NO_DEVICE;
-  if (hipStreamSynchronize(rx->last) != hipSuccess) return UGO_FEC_ERR_HIP;
+  if (hipStreamSynchronize(rx->last) != hipSuccess || stream_rx_sync_sets(rx) != hipSuccess) return UGO_FEC_ERR_HIP;
   return hip_status(hipMemcpy(host_out, &rx->rec->pub, sizeof(*host_out), hipMemcpyDeviceToHost));
 }
 
@@ -2340,6 +2363,134 @@ int ugo_fec_stream_rx_window(ugo_stream_rx* rx, uint8_t** window_dev, size_t* wi
   *window_dev = rx->win;
   *window_bytes = rx->cap;
   return UGO_FEC_OK;
+}
+
+// ---------------------------------------------------------------- receive-window sets
+int ugo_fec_stream_set_create(ugo_fec* c, ugo_stream_rx* const* rxs, size_t nconn, ugo_stream_rx_set** out) {
+  static_assert(sizeof(ugo::kern::StreamSetEntry) == 56, "a table entry is 56 bytes");
+  if (out) *out = nullptr;
+  if (!c || !rxs || !out || nconn == 0 || nconn > ugo::kern::kSetMaxConn) return UGO_FEC_ERR_INVALID_ARG;
+  for (size_t i = 0; i < nconn; ++i)
+    if (!rxs[i] || rxs[i]->ctx != c) return UGO_FEC_ERR_INVALID_ARG;
+  {  // a window listed twice: two table entries over one record would make the rule's atomics meaningless
+    std::vector<ugo_stream_rx*> sorted(rxs, rxs + nconn);
+    std::sort(sorted.begin(), sorted.end());
+    if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) return UGO_FEC_ERR_INVALID_ARG;
+  }
+  if (c->poisoned) return UGO_FEC_ERR_HIP;
+  DeviceGuard g(c->device);
+  if (!g.ok) return UGO_FEC_ERR_NO_DEVICE;
+  ugo_stream_rx_set* set = new (std::nothrow) ugo_stream_rx_set();
+  if (!set) return UGO_FEC_ERR_HIP;
+  set->ctx = c;
+  std::vector<ugo::kern::StreamSetEntry> host(nconn);
+  size_t max_cap = 0;
+  for (size_t i = 0; i < nconn; ++i) {
+    ugo_stream_rx* rx = rxs[i];
+    const size_t words = rx->cap / 64;
+    host[i] = {rx->win, rx->bits, rx->bits + words, rx->bits + 2 * words, rx->bits + 3 * words, rx->rec, rx->cap};
+    max_cap = std::max(max_cap, rx->cap);
+  }
+  set->wblocks = ugo::kern::stream_set_wblocks(max_cap);
+  set->rblocks = ugo::kern::stream_set_rblocks(max_cap, static_cast<uint32_t>(nconn));
+  if (hipMalloc(&set->table, nconn * sizeof(host[0])) != hipSuccess ||
+      hipMalloc(&set->gathered, nconn * sizeof(ugo_stream_rx_state)) != hipSuccess ||
+      hipMemcpy(set->table, host.data(), nconn * sizeof(host[0]), hipMemcpyHostToDevice) != hipSuccess) {
+    (void)hipGetLastError();
+    ugo_fec_stream_set_destroy(set);
+    return UGO_FEC_ERR_HIP;
+  }
+  set->members.assign(rxs, rxs + nconn);
+  for (ugo_stream_rx* rx : set->members) rx->sets.push_back(set);
+  *out = set;
+  return UGO_FEC_OK;
+}
+
+void ugo_fec_stream_set_destroy(ugo_stream_rx_set* set) {
+  if (!set) return;
+  {
+    DeviceGuard g(set->ctx->device);
+    if (set->used) (void)hipStreamSynchronize(set->last);
+    (void)hipFree(set->table);
+    (void)hipFree(set->gathered);
+  }
+  for (ugo_stream_rx* rx : set->members)
+    rx->sets.erase(std::remove(rx->sets.begin(), rx->sets.end(), set), rx->sets.end());
+  delete set;
+}
+
+int ugo_fec_stream_set_deliver(ugo_stream_rx_set* set, const uint8_t* pkts, size_t slot, const uint8_t* pad,
+                               const ugo_pkt_info* info, const ugo_pkt_segment* segs, size_t max_segments,
+                               size_t npk, const uint32_t* conn_of, uint8_t* seg_status, void* stream) {
+  if (!set) return UGO_FEC_ERR_INVALID_ARG;
+  ugo_fec* c = set->ctx;
+  if (c->poisoned) return UGO_FEC_ERR_HIP;
+  if (npk == 0) return UGO_FEC_OK;
+  if (!pkts || !info || !segs || !conn_of || !seg_status || slot % 16 || slot == 0 || slot > 0xffff ||
+      reinterpret_cast<uintptr_t>(pkts) % 16 || (pad && reinterpret_cast<uintptr_t>(pad) % 16) ||
+      reinterpret_cast<uintptr_t>(conn_of) % 4 || max_segments == 0 || max_segments > 0xffff ||
+      npk > (size_t(1) << 31))
+    return UGO_FEC_ERR_INVALID_ARG;
+  DeviceGuard g(c->device);
+  if (!g.ok) return UGO_FEC_ERR_NO_DEVICE;
+  if (!device_view(pkts) || !device_view(pad) || !device_view(info) || !device_view(segs) ||
+      !device_view(conn_of) || !device_view(seg_status))
+    return UGO_FEC_ERR_INVALID_ARG;
+  TimerScope ts(c);
+  ugo::kern::StreamSetArgs a{};
+  a.pkts = pkts;
+  a.pad = pad;
+  a.info = info;
+  a.segs = segs;
+  a.seg_status = seg_status;
+  a.conn_of = conn_of;
+  a.table = set->table;
+  a.npk = npk;
+  a.slot = slot;
+  a.nconn = static_cast<uint32_t>(set->members.size());
+  a.max_segments = static_cast<uint32_t>(max_segments);
+  a.wblocks = set->wblocks;
+  set->last = static_cast<hipStream_t>(stream);
+  set->used = true;
+  return hip_status(ugo::kern::launch_stream_set_deliver(a, set->last));
+}
+
+int ugo_fec_stream_set_read(ugo_stream_rx_set* set, uint8_t* dst, const uint64_t* dst_off, const uint64_t* n,
+                            uint64_t* n_read, uint8_t* eof, void* stream) {
+  if (!set || !n || !n_read || (dst && !dst_off) || reinterpret_cast<uintptr_t>(n) % 8 ||
+      reinterpret_cast<uintptr_t>(n_read) % 8 || reinterpret_cast<uintptr_t>(dst_off) % 8)
+    return UGO_FEC_ERR_INVALID_ARG;
+  ugo_fec* c = set->ctx;
+  if (c->poisoned) return UGO_FEC_ERR_HIP;
+  DeviceGuard g(c->device);
+  if (!g.ok) return UGO_FEC_ERR_NO_DEVICE;
+  if (!dst) dst_off = nullptr;
+  if (!device_view(dst) || !device_view(dst_off) || !device_view(n) || !device_view(n_read) || !device_view(eof))
+    return UGO_FEC_ERR_INVALID_ARG;
+  TimerScope ts(c);
+  ugo::kern::StreamSetReadArgs a{};
+  a.table = set->table;
+  a.dst = dst;
+  a.dst_off = dst_off;
+  a.n = n;
+  a.n_read = reinterpret_cast<unsigned long long*>(n_read);
+  a.eof = eof;
+  a.nconn = static_cast<uint32_t>(set->members.size());
+  a.rblocks = set->rblocks;
+  set->last = static_cast<hipStream_t>(stream);
+  set->used = true;
+  return hip_status(ugo::kern::launch_stream_set_read(a, set->last));
+}
+
+int ugo_fec_stream_set_state(ugo_stream_rx_set* set, ugo_stream_rx_state* host_out) {
+  if (!set || !host_out) return UGO_FEC_ERR_INVALID_ARG;
+  DeviceGuard g(set->ctx->device);
+  if (!g.ok) return UGO_FEC_ERR_NO_DEVICE;
+  const uint32_t nconn = static_cast<uint32_t>(set->members.size());
+  if (ugo::kern::launch_stream_set_gather(set->table, nconn, set->gathered, set->last) != hipSuccess ||
+      hipStreamSynchronize(set->last) != hipSuccess)
+    return UGO_FEC_ERR_HIP;
+  return hip_status(hipMemcpy(host_out, set->gathered, nconn * sizeof(*host_out), hipMemcpyDeviceToHost));
 }
 
 int ugo_fec_rc4_keystream(const uint8_t* key, size_t key_len, uint8_t* out, size_t n) {

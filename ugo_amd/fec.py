@@ -118,6 +118,8 @@ STREAM_OVERLAP = 4
 STREAM_TOO_MANY_GAPS = 5
 STREAM_MAX_GAPS = 50
 STREAM_MIN_WINDOW = 4096
+STREAM_NO_CONN = 0xffffffff   # conn_of: the packet belongs to no member of the set
+STREAM_SET_MAX_CONN = 1 << 20
 STREAM_STATE_DTYPE = np.dtype([("read_pos", "<u8"), ("head_off", "<u8"), ("hi", "<u8"), ("readable", "<u8"),
                                ("accepted", "<u8"), ("duplicate", "<u8"), ("out_of_window", "<u8"),
                                ("skipped_packets", "<u8"), ("ordered_segments", "<u8"), ("err_packet", "<u8"),
@@ -170,6 +172,12 @@ def load_library(path: str = LIB_PATH):
     lib.ugo_fec_stream_read.argtypes = [vp, vp, sz, vp, vp, vp]
     lib.ugo_fec_stream_rx_state.argtypes = [vp, vp]
     lib.ugo_fec_stream_rx_window.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(sz)]
+    lib.ugo_fec_stream_set_create.argtypes = [vp, vp, sz, ctypes.POINTER(vp)]
+    lib.ugo_fec_stream_set_destroy.argtypes = [vp]
+    lib.ugo_fec_stream_set_destroy.restype = None
+    lib.ugo_fec_stream_set_deliver.argtypes = [vp, vp, sz, vp, vp, vp, sz, sz, vp, vp, vp]
+    lib.ugo_fec_stream_set_read.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+    lib.ugo_fec_stream_set_state.argtypes = [vp, vp]
     lib.ugo_fec_reconstruct_rows.argtypes = [vp, vp, vp, sz, sz, vp, sz, sz, u, vp, vp]
     lib.ugo_fec_lossy_groups.argtypes = [vp, vp, sz, u, vp, vp, vp]
     lib.ugo_fec_rx_recover_host.argtypes = [vp, vp, sz, vp, sz, vp, ctypes.c_uint64, sz, sz, vp, vp, vp, sz, sz, vp,
@@ -815,6 +823,101 @@ class StreamRx:
         p, n = ctypes.c_void_p(), ctypes.c_size_t()
         _raise(load_library().ugo_fec_stream_rx_window(self._h, ctypes.byref(p), ctypes.byref(n)))
         return torch.as_tensor(_DeviceBytes(p.value, n.value, self), device=torch.device("cuda", self.device))
+
+
+class StreamRxSet:
+    """An ordered set of receive windows (ugo_fec_stream_set_*, include/ugo_stream.h):
+    one deliver for a batch that holds the packets of many connections, one read
+    for all of them.  The set does not own its members; close it before them."""
+
+    def __init__(self, enc: Encoder, rxs):
+        rxs = list(rxs)
+        self.check_members(enc, rxs)
+        arr = (ctypes.c_void_p * len(rxs))(*[rx._h.value for rx in rxs])
+        h = ctypes.c_void_p()
+        _raise(load_library().ugo_fec_stream_set_create(enc._h, ctypes.addressof(arr), len(rxs), ctypes.byref(h)))
+        self._h, self._enc, self.rxs = h, enc, rxs  # context and members must outlive the set
+        self.nconn = len(rxs)
+        self.device = enc.device
+
+    @staticmethod
+    def check_members(enc, rxs):
+        _require(0 < len(rxs) <= STREAM_SET_MAX_CONN, f"a set holds 1 to {STREAM_SET_MAX_CONN} windows")
+        _require(all(isinstance(rx, StreamRx) and getattr(rx, "_h", None) for rx in rxs), "members must be open StreamRx")
+        _require(all(rx._enc is enc for rx in rxs), "every member must belong to the set's context")
+        _require(len({id(rx) for rx in rxs}) == len(rxs), "a window may be listed once")
+
+    @staticmethod
+    def check_conn_of(conn_of, npk: int):
+        _require(conn_of.is_contiguous() and conn_of.element_size() == 4 and conn_of.numel() == npk and
+                 not conn_of.dtype.is_floating_point, "conn_of must be npackets contiguous 32-bit integers")
+
+    def check_per_conn(self, t, element_size: int, name: str):
+        _require(t.is_contiguous() and t.element_size() == element_size and t.numel() == self.nconn and
+                 not t.dtype.is_floating_point, f"{name} must be nconn contiguous {8 * element_size}-bit integers")
+
+    def close(self):
+        if getattr(self, "_h", None):
+            load_library().ugo_fec_stream_set_destroy(self._h)
+            self._h = None
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def deliver(self, pkts, info, segs, conn_of, pad=None, stream=None, out=None):
+        """ugo_fec_stream_set_deliver: StreamRx.deliver with conn_of, int32 [npk]
+        in device or pinned host memory -- the member index of each packet
+        (STREAM_NO_CONN as -1, or any index >= nconn: no connection).  Returns
+        seg_status, uint8 [npk, max_segments].  Nothing is synchronised."""
+        npk, slot = pkts.shape
+        _require(pkts.is_contiguous() and pkts.element_size() == 1)
+        _require(info.is_contiguous() and info.element_size() == 1 and tuple(info.shape) == (npk, 64))
+        _require(segs.is_contiguous() and segs.element_size() == 1 and segs.dim() == 3 and segs.shape[0] == npk and
+                 segs.shape[2] == 16)
+        if pad is not None:
+            _require(pad.is_contiguous() and pad.element_size() == 1 and pad.numel() >= slot)
+        StreamRx.check_batch(slot, pkts.data_ptr(), None if pad is None else pad.data_ptr())
+        self.check_conn_of(conn_of, npk)
+        max_segments = segs.shape[1]
+        if out is None:
+            out = torch.empty((npk, max_segments), dtype=torch.uint8, device=pkts.device)
+        _require(tuple(out.shape) == (npk, max_segments) and out.is_contiguous() and out.element_size() == 1)
+        _raise(load_library().ugo_fec_stream_set_deliver(
+            self._h, pkts.data_ptr(), slot, None if pad is None else pad.data_ptr(), info.data_ptr(),
+            segs.data_ptr(), max_segments, npk, conn_of.data_ptr(), out.data_ptr(), _stream_handle(stream)))
+        return out
+
+    def read(self, n, dst=None, dst_off=None, stream=None, n_read=None, eof=None):
+        """ugo_fec_stream_set_read: n = int64 [nconn] bytes wanted per member (0
+        skips it), dst = uint8 buffer or None to discard, dst_off = int64 [nconn]
+        offsets into dst (the caller keeps the ranges disjoint and inside dst).
+        Returns (n_read int64 [nconn], eof uint8 [nconn]); both may be given.
+        Operands in device or pinned host memory.  Nothing is synchronised."""
+        dev = torch.device("cuda", self.device)
+        self.check_per_conn(n, 8, "n")
+        if dst is not None:
+            _require(dst.is_contiguous() and dst.element_size() == 1)
+            _require(dst_off is not None, "dst needs dst_off")
+            self.check_per_conn(dst_off, 8, "dst_off")
+        if n_read is None:
+            n_read = torch.zeros(self.nconn, dtype=torch.int64, device=dev)
+        if eof is None:
+            eof = torch.zeros(self.nconn, dtype=torch.uint8, device=dev)
+        self.check_per_conn(n_read, 8, "n_read")
+        self.check_per_conn(eof, 1, "eof")
+        _raise(load_library().ugo_fec_stream_set_read(
+            self._h, None if dst is None else dst.data_ptr(), None if dst is None else dst_off.data_ptr(),
+            n.data_ptr(), n_read.data_ptr(), eof.data_ptr(), _stream_handle(stream)))
+        return n_read, eof
+
+    def states(self) -> np.ndarray:
+        """The members' records (STREAM_STATE_DTYPE [nconn]); waits for the last call on the set."""
+        out = np.zeros(self.nconn, STREAM_STATE_DTYPE)
+        _raise(load_library().ugo_fec_stream_set_state(self._h, out.ctypes.data))
+        return out
 
 
 def rc4_keystream(key: bytes, n: int) -> bytes:

@@ -201,7 +201,13 @@ int ugo_fec_stream_rx_window(ugo_stream_rx* rx, uint8_t** window_dev, size_t* wi
  * the set's calls.  The launches report as kernel classes
  * UGO_FEC_KERNEL_STREAM_DELIVER and UGO_FEC_KERNEL_STREAM_READ.  Checked on
  * the device against one rule per member, where blocks mix connections
- * (tests/stream_set_harness.py, tests/test_stream_set.py). */
+ * (tests/stream_set_harness.py, tests/test_stream_set.py), and at the launch
+ * shapes of large and unequal sets (tests/test_stream_set_sizes.py): reads,
+ * bitmap passes and gap counts with up to 256 blocks per connection over
+ * windows of 4 KiB to 4 MiB in one set, wrapped windows, a status array that
+ * is not 16-B aligned with three segment slots per packet, a member across
+ * 2^32 beside one at 0, lying descriptors between another member's packets,
+ * and a set of 32,769 members. */
 #define UGO_STREAM_NO_CONN 0xffffffffu
 
 typedef struct ugo_stream_rx_set ugo_stream_rx_set;

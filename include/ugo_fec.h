@@ -65,7 +65,8 @@ extern "C" {
  *    ugo_fec_packet_encode with ugo_pkt_status 7-9 (ugo_pkt.h) and
  *    UGO_FEC_KERNEL_PACKET_ENCODE; the ugo_fec_stream_* entry points with
  *    ugo_stream_status (ugo_stream.h), UGO_FEC_KERNEL_STREAM_DELIVER and
- *    UGO_FEC_KERNEL_STREAM_READ. */
+ *    UGO_FEC_KERNEL_STREAM_READ; the send windows, ugo_fec_stream_tx_*
+ *    (ugo_stream.h), with UGO_PKT_OUT_OF_WINDOW and UGO_FEC_KERNEL_STREAM_TX. */
 #define UGO_FEC_ABI_VERSION 9
 
 /* Status codes.  1..5 map 1:1 onto the klauspost/reedsolomon error values
@@ -473,6 +474,7 @@ int ugo_fec_rc4_keystream(const uint8_t* key, size_t key_len, uint8_t* out, size
 #define UGO_FEC_KERNEL_PACKET_ENCODE 8 /* ugo_fec_packet_encode                 */
 #define UGO_FEC_KERNEL_STREAM_DELIVER 9 /* ugo_fec_stream_deliver (ugo_stream.h)  */
 #define UGO_FEC_KERNEL_STREAM_READ 10   /* ugo_fec_stream_read                    */
+#define UGO_FEC_KERNEL_STREAM_TX 11     /* ugo_fec_stream_tx_set_* but encode     */
 
 typedef struct ugo_fec_launch_time {
   uint32_t kernel; /* UGO_FEC_KERNEL_* */

@@ -56,7 +56,8 @@ typedef enum ugo_pkt_status {
                                           encode: n_ranges / n_segments above the caps, or the packet exceeds its slot */
   UGO_PKT_INCONSISTENT_LARGEST_ACKED = 7, /* encode: errInconsistentAckLargestAcked (ugo/packet.go:367-369) */
   UGO_PKT_INCONSISTENT_LOWEST_ACKED = 8,  /* encode: errInconsistentAckLowestAcked (ugo/packet.go:370-372) */
-  UGO_PKT_INCONSISTENT_RANGE_COUNT = 9    /* encode: "BUG: Inconsistent number of ACK ranges written" (ugo/packet.go:425-427) */
+  UGO_PKT_INCONSISTENT_RANGE_COUNT = 9,   /* encode: "BUG: Inconsistent number of ACK ranges written" (ugo/packet.go:425-427) */
+  UGO_PKT_OUT_OF_WINDOW = 10              /* ugo_fec_stream_tx_set_encode (ugo_stream.h): a segment outside its send window */
 } ugo_pkt_status;
 
 /* Decoded fixed fields of one packet (64 bytes). */

@@ -248,6 +248,210 @@ int ugo_fec_stream_set_read(ugo_stream_rx_set* set, uint8_t* dst, const uint64_t
  * call on the set: gathered on the device and copied out in one transfer. */
 int ugo_fec_stream_set_state(ugo_stream_rx_set* set, ugo_stream_rx_state* host_out /* [nconn] */);
 
+/* ---- Send windows: Conn.Write, PopSegments and encode per set -------------
+ *
+ * Added within ABI version 9: the presence of the ugo_fec_stream_tx_* symbols
+ * is the feature test.  The transmit mirror of the receive-window sets:
+ *
+ *   Conn.Write            ugo/conn.go:247-275
+ *   lenOfDataForWriting,
+ *   getDataForWriting     ugo/conn.go:753-779   (advances writeOffset)
+ *   PopSegments,
+ *   popSegmentsForRetransmission, popNormalSegments,
+ *   maybeSplitOffFrame    ugo/segment_sender.go:18-99
+ *   Conn.sendPacket       ugo/conn.go:521-640   PopSegments(maxPacketSize - 40),
+ *                                               lastPacketNumber++, encode, encrypt
+ *   retransmitted segments go to the back of retransmissionQueue
+ *                         ugo/conn.go:565-568, ugo/packet_sender.go:262-285
+ *
+ * A send window (ugo_stream_tx) holds a connection's unsent and
+ * unacknowledged stream bytes on the device:
+ *   W     the window, cap = window_bytes, a power of two in [4096, 2^31];
+ *         stream byte x lives at W[x & (cap-1)]
+ *   Q     the retransmission queue, a FIFO ring of rq_cap entries
+ *         (ugo_stream_tx_rq_entry); the queue is Q[(rq_head + k) % rq_cap],
+ *         k < rq_len
+ *   a record, mirrored by ugo_stream_tx_state; base <= write_pos <= tail <=
+ *   base + cap
+ * Three hot calls per batch -- write, plan, encode -- keep the send chain on
+ * the device from Conn.Write to the slots ugo_fec_tx_assemble consumes.  ARQ,
+ * ACK processing and congestion control stay on the host and hand these calls
+ * a packet budget (plan), the segments to retransmit (retransmit) and how far
+ * the peer has acknowledged (release).
+ *
+ * THE RULE of plan, with M = max_payload (the reference's maxPacketSize - 40 =
+ * 1436) and H = 4.  Member c, at most budget_eff[c] times:
+ *
+ *   cur = 0, segs = []
+ *   while queue not empty and len(segs) < max_segments:
+ *       if cur + H >= M: break                                   (a)
+ *       cur += H; s = queue front; room = M - cur
+ *       if s.len > room: emit (s.offset, room); s.offset += room;
+ *                        s.len -= room; cur += room; break
+ *       pop; emit (s.offset, s.len); cur += s.len
+ *   rem = M - cur; pending = tail - write_pos
+ *   if rem > H and pending > 0 and len(segs) < max_segments:     (a)
+ *       n = min(pending, rem - H); emit (write_pos, n); write_pos += n
+ *   if segs is empty: stop
+ *   packet_number = ++last_packet_number
+ *
+ * budget_eff[c] = min(budget[c], max(0, max_packets - sum of budget[c'] for
+ * c' < c)): a budget array that asks for more than the caller's arrays hold is
+ * clamped, never followed.
+ *
+ * DEVIATIONS from the reference, all on purpose:
+ *   (a) no empty segment from plan.  popSegmentsForRetransmission tests
+ *       currentLen + 4 > maxLen and popNormalSegments tests 4 > maxBytes, so
+ *       with exactly 4 bytes of room left the reference emits a segment with
+ *       no data -- which the receiver reads as a FIN.  Here a piece is emitted
+ *       only if at least one byte of it fits; FIN is the caller's packet.  The
+ *       reference's packets with their empty segments removed are the rule's
+ *       packets, and the final state (queue, write_pos) is identical.
+ *   (b) the window bound: Go's Write hands over a slice of any size and blocks
+ *       until it is sent; write here is partial and never waits.
+ *   (c) the segment cap: a packet closes when it holds max_segments segments.
+ *       The reference has no cap (a packet of 1-byte retransmissions could
+ *       hold 287).
+ *   (d) the empty write: a zero-length write is a no-op.  In the reference
+ *       Write([]byte{}) makes getDataForWriting return an empty non-nil slice,
+ *       which is sent as an empty segment.
+ * Checked on the CPU against a literal restatement of the Go loop
+ * (tests/stream_tx_ref.py) and on the device against one rule per member
+ * (tests/stream_tx_harness.py, tests/test_stream_tx.py).
+ *
+ * Every operand array is in device or pinned host memory (pageable memory is
+ * rejected); every call is stream-ordered with no host synchronisation and no
+ * host-to-device copy of its own; the caller orders the calls on one set.
+ * Argument errors return UGO_FEC_ERR_INVALID_ARG before any launch, with
+ * nothing written.  There are no single-connection entry points: a set of one
+ * member is the single-connection form.  write, release, retransmit, plan and
+ * the state gather report as kernel class UGO_FEC_KERNEL_STREAM_TX, encode as
+ * UGO_FEC_KERNEL_PACKET_ENCODE. */
+#define UGO_STREAM_TX_MAX_WINDOW 0x80000000u
+
+/* Per-entry result of ugo_fec_stream_tx_set_retransmit. */
+typedef enum ugo_stream_tx_rq_status {
+  UGO_STREAM_TX_RQ_QUEUED = 1,
+  UGO_STREAM_TX_RQ_REJECTED = 2, /* len 0 or > 0xffff, not inside [base, write_pos), conn_of >= nconn */
+  UGO_STREAM_TX_RQ_FULL = 3,     /* the queue is full: this entry and the connection's later ones */
+  UGO_STREAM_TX_RQ_UNSORTED = 4  /* conn_of decreases somewhere: nothing of the call was applied */
+} ugo_stream_tx_rq_status;
+
+/* One retransmission-queue entry (16 bytes). */
+typedef struct ugo_stream_tx_rq_entry {
+  uint64_t offset;
+  uint32_t len;
+  uint32_t reserved;
+} ugo_stream_tx_rq_entry;
+
+/* Host mirror of a send window's record (80 bytes). */
+typedef struct ugo_stream_tx_state {
+  uint64_t base;                /* lowest retained stream offset */
+  uint64_t write_pos;           /* Conn.writeOffset: the next byte not yet packetised */
+  uint64_t tail;                /* end of the bytes written */
+  uint64_t last_packet_number;  /* Conn.lastPacketNumber */
+  uint64_t packets;             /* counters, cumulative over calls */
+  uint64_t segments;
+  uint64_t bytes_new;
+  uint64_t bytes_retransmitted;
+  uint64_t rq_rejected;         /* retransmit entries answered REJECTED or FULL */
+  uint32_t rq_len;              /* entries queued */
+  uint32_t rq_head;             /* ring index of the queue's front */
+} ugo_stream_tx_state;
+
+typedef struct ugo_stream_tx ugo_stream_tx;
+typedef struct ugo_stream_tx_set ugo_stream_tx_set;
+
+/* A send window on ctx's device, everything zeroed, base = write_pos = tail =
+ * start_offset and last_packet_number = start_packet_number (the reference
+ * starts both at 0; other values adopt a connection mid-life).  window_bytes
+ * a power of two in [UGO_STREAM_MIN_WINDOW, UGO_STREAM_TX_MAX_WINDOW],
+ * 1 <= rq_cap <= 2^24.  ctx must outlive it. */
+int ugo_fec_stream_tx_create(ugo_fec* ctx, size_t window_bytes, size_t rq_cap, uint64_t start_offset,
+                             uint64_t start_packet_number, ugo_stream_tx** out);
+void ugo_fec_stream_tx_destroy(ugo_stream_tx* tx);
+
+/* The window and the queue ring themselves (device memory), for consumers and
+ * tests that look at them in place, after synchronising the set's stream. */
+int ugo_fec_stream_tx_window(ugo_stream_tx* tx, uint8_t** window_dev, size_t* window_bytes);
+int ugo_fec_stream_tx_queue(ugo_stream_tx* tx, ugo_stream_tx_rq_entry** rq_dev, size_t* rq_cap);
+
+/* An ordered list of existing send windows (sizes may differ).  Ownership,
+ * lifetime, duplicate-member and nconn <= 2^20 rules as for
+ * ugo_fec_stream_set_create: the set does not own its members, destroy the
+ * set first; INVALID_ARG for a NULL argument, nconn == 0 or > 2^20, a NULL
+ * member, a member of another context or one listed twice.  The member table
+ * and the plan's scratch are made here, once. */
+int ugo_fec_stream_tx_set_create(ugo_fec* ctx, ugo_stream_tx* const* txs, size_t nconn, ugo_stream_tx_set** out);
+void ugo_fec_stream_tx_set_destroy(ugo_stream_tx_set* set);
+
+/* Conn.Write that never waits (deviation (b)), for every member: m = min(n[c],
+ * cap - (tail - base)) bytes go from src + src_off[c] to W[(tail + k) &
+ * (cap-1)] (two pieces at the wrap), tail += m, n_written[c] = m.  n[c] == 0
+ * leaves the member untouched (deviation (d)) and gives n_written[c] = 0.  src
+ * may have any alignment; src_off, n and n_written are uint64[nconn].  Window
+ * bytes outside [tail, tail + m) are neither written nor read-modify-written.
+ * The caller keeps the source ranges readable; the call does not check them. */
+int ugo_fec_stream_tx_set_write(ugo_stream_tx_set* set, const uint8_t* src, const uint64_t* src_off,
+                                const uint64_t* n, uint64_t* n_written, void* stream);
+
+/* Per member: base = max(base, min(upto[c], write_pos, the lowest offset still
+ * held in the member's retransmission queue)).  upto is uint64[nconn]. */
+int ugo_fec_stream_tx_set_release(ugo_stream_tx_set* set, const uint64_t* upto, void* stream);
+
+/* Append m entries (conn_of uint32, offset uint64, len uint32) to the
+ * members' queues, in index order within a connection.  conn_of must be
+ * non-decreasing over the list; if any conn_of[j] < conn_of[j-1] nothing is
+ * applied and every status is UGO_STREAM_TX_RQ_UNSORTED.  Otherwise status[j]
+ * (uint8[m]) is a ugo_stream_tx_rq_status; REJECTED and FULL entries count in
+ * the member's rq_rejected (an entry with conn_of >= nconn in no record).
+ * A cold path: the list is the loss rate's share of a batch.  m == 0 is a
+ * no-op. */
+int ugo_fec_stream_tx_set_retransmit(ugo_stream_tx_set* set, const uint32_t* conn_of, const uint64_t* offset,
+                                     const uint32_t* len, size_t m, uint8_t* status, void* stream);
+
+/* The loop of Conn.sendPacket for every member: THE RULE above.  budget is
+ * uint32[nconn]; 16 <= max_payload <= 0xffff; 1 <= max_segments <= 0xffff;
+ * max_packets <= 2^31.  The packets are compact and connection-major: member
+ * c's packets are batch indices [first_packet[c], first_packet[c] +
+ * n_packets[c]) (uint64[nconn], uint32[nconn]), members in set order; *total
+ * (uint64) is the number of packets planned.  For i < total the whole 64-byte
+ * info[i] is written (flags 0, packet_number, n_segments, everything else
+ * zero), segs[i][0 .. n_segments) get offset, len, avail = len and data_off =
+ * offset & (cap-1), and conn_of[i] = c.  For total <= i < max_packets,
+ * conn_of[i] = UGO_STREAM_NO_CONN and nothing else of packet i is written;
+ * segment entries at or past n_segments keep the caller's bytes.  A member
+ * with budget_eff == 0 or nothing to send keeps its record bit for bit, gets
+ * n_packets = 0 and first_packet = where its packets would have started.
+ * first_packet tells the caller where to patch a SACK or a stop-waiting into a
+ * connection's first packet before encode; ACK-only, stop-waiting-only, FIN
+ * and RST packets are the caller's, appended by it. */
+int ugo_fec_stream_tx_set_plan(ugo_stream_tx_set* set, const uint32_t* budget, size_t max_payload,
+                               size_t max_segments, size_t max_packets, ugo_pkt_info* info, ugo_pkt_segment* segs,
+                               uint32_t* conn_of, uint64_t* first_packet, uint32_t* n_packets, uint64_t* total,
+                               void* stream);
+
+/* ugo_fec_packet_encode (ugo_pkt.h) with two differences.  The bytes of
+ * segment j of packet i are stream bytes [offset, offset + len) of member
+ * conn_of[i], read at W[x & (cap-1)] -- data_off and avail are ignored, a
+ * segment may straddle the wrap point.  And validation: a packet one of whose
+ * segments is not inside its member's [base, tail) (an empty segment:
+ * base <= offset <= tail) gets status UGO_PKT_OUT_OF_WINDOW, wire_lens[i] = 0
+ * and an untouched slot (checked after the n_ranges / n_segments caps, before
+ * everything else); a packet with conn_of[i] >= nconn gets status 0,
+ * wire_lens[i] = 0 and an untouched slot.  Header bytes, SACK, framing, the
+ * pad, statuses 6-9, the argument rules and the write extent -- exactly
+ * [0, round_up(len, 16)) of a slot, each 16-B chunk once, zeros past the
+ * packet's end -- are those of ugo_fec_packet_encode. */
+int ugo_fec_stream_tx_set_encode(ugo_stream_tx_set* set, const ugo_pkt_info* info, const uint64_t* ranges,
+                                 size_t max_ranges, const ugo_pkt_segment* segs, size_t max_segments,
+                                 const uint32_t* conn_of, size_t npackets, const uint8_t* pad, unsigned flags,
+                                 uint8_t* wire, size_t slot, uint16_t* wire_lens, uint8_t* status, void* stream);
+
+/* The nconn records, in set order, after synchronising the stream of the last
+ * call on the set. */
+int ugo_fec_stream_tx_set_state(ugo_stream_tx_set* set, ugo_stream_tx_state* host_out /* [nconn] */);
+
 #ifdef __cplusplus
 }
 #endif

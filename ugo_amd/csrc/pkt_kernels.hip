@@ -373,15 +373,87 @@ __device__ __forceinline__ GapBlocks gap_blocks(uint64_t prev_first, uint64_t fi
   return g;
 }
 
+// Where a packet's segment bytes come from: the source policy of
+// encode_header and k_packet_encode.  FlatSrc is ugo_fec_packet_encode's
+// payload pointer (segment at payload + i*payload_stride + data_off); WinSrc
+// is ugo_fec_stream_tx_set_encode's send window of member conn_of[i] (stream
+// byte x at win[x & (cap-1)], include/ugo_stream.h), which also refuses a
+// packet of no member and a segment outside [base, tail).
+struct FlatSrc {
+  typedef PktEncArgs Args;
+  static constexpr bool kStash = false;  // phase B recomputes the packet's source from the arguments
+  struct Seg {
+    const uint8_t* s;
+    __device__ __forceinline__ u32x4 ld16(uint32_t k) const { return ldu16(s + k); }
+    __device__ __forceinline__ uint32_t byte(uint32_t k) const { return s[k]; }
+  };
+  const uint8_t* p;
+  __device__ __forceinline__ FlatSrc(const Args& a, uint64_t i) : p(a.payload + i * a.payload_stride) {}
+  __device__ __forceinline__ bool member() const { return true; }
+  __device__ __forceinline__ bool holds(const ugo_pkt_segment*, uint32_t) const { return true; }
+  __device__ __forceinline__ Seg seg(const ugo_pkt_segment& g) const { return Seg{p + g.data_off}; }
+};
+
+struct WinSrc {
+  typedef PktEncSetArgs Args;
+  // phase A leaves the member's window in LDS: phase B then starts on the bytes
+  // without the dependent loads of conn_of[i] and the table entry
+  static constexpr bool kStash = true;
+  struct Stash {
+    const uint8_t* win;
+    uint64_t mask;
+  };
+  struct Seg {
+    const uint8_t* win;
+    uint64_t mask, o;
+    __device__ __forceinline__ uint32_t byte(uint32_t k) const { return win[(o + k) & mask]; }
+    __device__ __forceinline__ u32x4 ld16(uint32_t k) const {
+      const uint64_t at = (o + k) & mask;
+      if (at + 16u <= mask + 1u) return ldu16(win + at);
+      uint32_t d[4] = {0u, 0u, 0u, 0u};  // the 16 bytes straddle the wrap point
+      for (uint32_t b = 0; b < 16u; ++b) d[b >> 2] |= static_cast<uint32_t>(win[(at + b) & mask]) << (8u * (b & 3u));
+      return u32x4{d[0], d[1], d[2], d[3]};
+    }
+  };
+  const uint8_t* win;
+  const ugo_stream_tx_state* rec;
+  uint64_t mask;
+  __device__ __forceinline__ WinSrc(const Args& a, uint64_t i) : win(nullptr), rec(nullptr), mask(0) {
+    const uint32_t c = a.conn_of[i];
+    if (c < a.nconn) {
+      const StreamTxEntry& e = a.table[c];
+      win = e.win;
+      rec = e.rec;
+      mask = e.cap - 1;
+    }
+  }
+  __device__ __forceinline__ explicit WinSrc(const Stash& st) : win(st.win), rec(nullptr), mask(st.mask) {}
+  __device__ __forceinline__ Stash stash() const { return Stash{win, mask}; }
+  __device__ __forceinline__ bool member() const { return win != nullptr; }
+  __device__ __forceinline__ bool holds(const ugo_pkt_segment* sg, uint32_t nseg) const {
+    const uint64_t base = rec->base, tail = rec->tail;
+    bool ok = true;
+    for (uint32_t j = 0; j < nseg; ++j) {
+      const uint64_t o = sg[j].offset;
+      ok = ok && o >= base && o <= tail && sg[j].len <= tail - o;
+    }
+    return ok;
+  }
+  __device__ __forceinline__ Seg seg(const ugo_pkt_segment& g) const { return Seg{win, mask, g.offset}; }
+};
+
 // Sizes packet i and, if the reference would encode it and it fits, writes
 // its header and boundary chunks.  Returns the status; pos0 = where the first
 // segment header starts, ns = segments to place (0 unless the status is OK).
-__device__ uint32_t encode_header(const PktEncArgs& a, uint64_t i, uint32_t& pos0, uint32_t& ns, uint32_t& total) {
+template <class Src>
+__device__ uint32_t encode_header(const typename Src::Args& a, const Src& P, uint64_t i, uint32_t& pos0, uint32_t& ns,
+                                  uint32_t& total) {
   const ugo_pkt_info& I = a.info[i];
   const uint32_t nr = I.n_ranges, nseg = I.n_segments;
   if (nr > a.max_ranges || nseg > a.max_segments) return kCapacity;
   const uint64_t* rg = a.ranges + i * 2ull * a.max_ranges;
   const ugo_pkt_segment* sg = a.segs + i * a.max_segments;
+  if (!P.holds(sg, nseg)) return UGO_PKT_OUT_OF_WINDOW;
   const uint64_t pn = I.packet_number, sw = I.stop_waiting;
   const uint64_t largest = I.largest_acked, in_order = I.largest_in_order;
   const bool has_sack = (I.flags & 0x80u) != 0;  // p.sack != nil
@@ -471,15 +543,15 @@ __device__ uint32_t encode_header(const PktEncArgs& a, uint64_t i, uint32_t& pos
     w.put_uvarint(sg[j].offset);
     w.put(L >> 8);  // binary.BigEndian uint16
     w.put(L);
-    const uint8_t* src = a.payload + i * a.payload_stride + sg[j].data_off;
+    const typename Src::Seg src = P.seg(sg[j]);
     if (L < 16u) {
-      for (uint32_t k = 0; k < L; ++k) w.put(src[k]);
+      for (uint32_t k = 0; k < L; ++k) w.put(src.byte(k));
       continue;
     }
     const uint32_t head = (16u - (w.pos & 15u)) & 15u;  // up to the next chunk boundary (< 16 <= L)
     const uint32_t interior = (L - head) & ~15u;         // whole chunks: phase B
     const uint32_t tail = L - head - interior;
-    const u32x4 H = ldu16(src), T = ldu16(src + L - 16u);
+    const u32x4 H = src.ld16(0u), T = src.ld16(L - 16u);
     for (uint32_t k = 0; k < head; ++k) w.put(byte_of(H, k));
     w.skip_chunks(interior);
     for (uint32_t k = 0; k < tail; ++k) w.put(byte_of(T, 16u - tail + k));
@@ -491,14 +563,23 @@ __device__ uint32_t encode_header(const PktEncArgs& a, uint64_t i, uint32_t& pos
   return kOK;
 }
 
-__global__ __launch_bounds__(256) void k_packet_encode(PktEncArgs a) {
+template <class Src>
+__device__ __forceinline__ typename Src::Stash* src_stash() {
+  __shared__ typename Src::Stash s[kEncPacketsPerBlock];
+  return s;
+}
+
+template <class Src>
+__global__ __launch_bounds__(256) void k_packet_encode(typename Src::Args a) {
   __shared__ uint32_t s_pos0[kEncPacketsPerBlock], s_ns[kEncPacketsPerBlock];
   const uint64_t first = blockIdx.x * static_cast<uint64_t>(kEncPacketsPerBlock);
   if (threadIdx.x < kEncPacketsPerBlock) {
     const uint64_t i = first + threadIdx.x;
     uint32_t pos0 = 0, ns = 0, total = 0;
     if (i < a.npk) {
-      const uint32_t st = encode_header(a, i, pos0, ns, total);
+      const Src P(a, i);
+      const uint32_t st = P.member() ? encode_header<Src>(a, P, i, pos0, ns, total) : kOK;
+      if constexpr (Src::kStash) src_stash<Src>()[threadIdx.x] = P.stash();
       a.status[i] = static_cast<uint8_t>(st);
       a.wire_lens[i] = static_cast<uint16_t>(st == kOK ? total : 0u);
     }
@@ -513,13 +594,18 @@ __global__ __launch_bounds__(256) void k_packet_encode(PktEncArgs a) {
     if (ns == 0) continue;
     const uint64_t i = first + t;
     const ugo_pkt_segment* sg = a.segs + i * a.max_segments;
-    const uint8_t* pay = a.payload + i * a.payload_stride;
+    const Src P = [&] {
+      if constexpr (Src::kStash)
+        return Src(src_stash<Src>()[t]);
+      else
+        return Src(a, i);
+    }();
     uint8_t* out = a.wire + i * a.slot;
     uint32_t pos = s_pos0[t];
     for (uint32_t j = 0; j < ns; ++j) {
       const uint32_t L = sg[j].len;
       pos += uvarint_len(sg[j].offset) + 2u;      // segment data at packet bytes [pos, pos + L)
-      const uint8_t* src = pay + sg[j].data_off;  // packet byte x of it is src[x - pos]
+      const typename Src::Seg src = P.seg(sg[j]);  // packet byte x of it is byte x - pos of the segment
       const uint32_t c0 = (pos + 15u) >> 4, c1 = (pos + L) >> 4;  // interior chunks [c0, c1)
       for (uint32_t c = c0 + hl; c < c1; c += 4u * kEncLanes) {
         u32x4 v[4];
@@ -527,7 +613,7 @@ __global__ __launch_bounds__(256) void k_packet_encode(PktEncArgs a) {
         for (uint32_t q = 0; q < 4; ++q) {
           const uint32_t cc = c + q * kEncLanes;
           if (cc < c1) {
-            v[q] = ldu16(src + (16u * cc - pos));
+            v[q] = src.ld16(16u * cc - pos);
             if (a.pad) v[q] ^= *reinterpret_cast<const u32x4*>(a.pad + 16u * cc);
           }
         }
@@ -554,7 +640,14 @@ hipError_t launch_packet_decode(const PktArgs& a, hipStream_t s) {
 hipError_t launch_packet_encode(const PktEncArgs& a, hipStream_t s) {
   if (a.npk == 0) return hipSuccess;
   const uint64_t blocks = (a.npk + kEncPacketsPerBlock - 1) / kEncPacketsPerBlock;
-  launch(kKPacketEncode, k_packet_encode, dim3(static_cast<uint32_t>(blocks)), dim3(256), 0, s, a);
+  launch(kKPacketEncode, k_packet_encode<FlatSrc>, dim3(static_cast<uint32_t>(blocks)), dim3(256), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_packet_encode_set(const PktEncSetArgs& a, hipStream_t s) {
+  if (a.npk == 0) return hipSuccess;
+  const uint64_t blocks = (a.npk + kEncPacketsPerBlock - 1) / kEncPacketsPerBlock;
+  launch(kKPacketEncode, k_packet_encode<WinSrc>, dim3(static_cast<uint32_t>(blocks)), dim3(256), 0, s, a);
   return hipGetLastError();
 }
 

@@ -5,6 +5,7 @@
 #include <cstdint>
 
 #include "../../include/ugo_pkt.h"
+#include "stream_tx_kernels.hpp"
 
 namespace ugo {
 namespace kern {
@@ -43,6 +44,16 @@ struct PktEncArgs {
 };
 
 hipError_t launch_packet_encode(const PktEncArgs& a, hipStream_t s);
+
+// ugo_fec_stream_tx_set_encode: the segment bytes come from the send window of
+// member conn_of[i] (payload and payload_stride are unused)
+struct PktEncSetArgs : PktEncArgs {
+  const uint32_t* conn_of;     // [npk]
+  const StreamTxEntry* table;  // [nconn]
+  uint32_t nconn;
+};
+
+hipError_t launch_packet_encode_set(const PktEncSetArgs& a, hipStream_t s);
 
 }  // namespace kern
 }  // namespace ugo

@@ -98,13 +98,14 @@ PKT_CAPACITY = 6
 PKT_INCONSISTENT_LARGEST_ACKED = 7  # packet_encode's per-packet statuses
 PKT_INCONSISTENT_LOWEST_ACKED = 8
 PKT_INCONSISTENT_RANGE_COUNT = 9
+PKT_OUT_OF_WINDOW = 10  # stream_tx set_encode: a segment outside its send window
 PKT_INFO_DTYPE = np.dtype([("packet_number", "<u8"), ("stop_waiting", "<u8"), ("largest_acked", "<u8"),
                            ("largest_in_order", "<u8"), ("delay_us", "<u8"), ("status", "<u4"),
                            ("payload_off", "<u4"), ("n_ranges", "<u2"), ("n_segments", "<u2"), ("flags", "u1"),
                            ("fec_flag_lo", "u1"), ("reserved", "u1", (10,))])
 # include/ugo_fec.h launch timing
 KERNEL_NAMES = {1: "encode", 2: "reconstruct", 3: "prepare", 4: "bytes", 5: "rx_assemble", 6: "tx_assemble",
-                7: "packet_decode", 8: "packet_encode", 9: "stream_deliver", 10: "stream_read"}
+                7: "packet_decode", 8: "packet_encode", 9: "stream_deliver", 10: "stream_read", 11: "stream_tx"}
 KERNEL_IDS = {v: k for k, v in KERNEL_NAMES.items()}
 LAUNCH_TIME_DTYPE = np.dtype([("kernel", "<u4"), ("ms", "<f4")])
 PKT_SEGMENT_DTYPE = np.dtype([("offset", "<u8"), ("data_off", "<u4"), ("len", "<u2"), ("avail", "<u2")])
@@ -126,6 +127,19 @@ STREAM_STATE_DTYPE = np.dtype([("read_pos", "<u8"), ("head_off", "<u8"), ("hi", 
                                ("err_segment", "<u4"), ("err", "<u4"), ("ngaps", "<u4"), ("head_valid", "u1"),
                                ("eof", "u1"), ("reserved", "u1", (2,))])
 assert STREAM_STATE_DTYPE.itemsize == 96
+# include/ugo_stream.h, send windows
+STREAM_TX_MAX_WINDOW = 1 << 31
+STREAM_TX_HEADER = 4  # frameHeaderLen of segment_sender.go: H of THE RULE
+STREAM_TX_RQ_QUEUED = 1
+STREAM_TX_RQ_REJECTED = 2
+STREAM_TX_RQ_FULL = 3
+STREAM_TX_RQ_UNSORTED = 4
+STREAM_TX_RQ_DTYPE = np.dtype([("offset", "<u8"), ("len", "<u4"), ("reserved", "<u4")])
+STREAM_TX_STATE_DTYPE = np.dtype([("base", "<u8"), ("write_pos", "<u8"), ("tail", "<u8"),
+                                  ("last_packet_number", "<u8"), ("packets", "<u8"), ("segments", "<u8"),
+                                  ("bytes_new", "<u8"), ("bytes_retransmitted", "<u8"), ("rq_rejected", "<u8"),
+                                  ("rq_len", "<u4"), ("rq_head", "<u4")])
+assert STREAM_TX_STATE_DTYPE.itemsize == 80 and STREAM_TX_RQ_DTYPE.itemsize == 16
 
 
 def load_library(path: str = LIB_PATH):
@@ -178,6 +192,21 @@ def load_library(path: str = LIB_PATH):
     lib.ugo_fec_stream_set_deliver.argtypes = [vp, vp, sz, vp, vp, vp, sz, sz, vp, vp, vp]
     lib.ugo_fec_stream_set_read.argtypes = [vp, vp, vp, vp, vp, vp, vp]
     lib.ugo_fec_stream_set_state.argtypes = [vp, vp]
+    u64 = ctypes.c_uint64
+    lib.ugo_fec_stream_tx_create.argtypes = [vp, sz, sz, u64, u64, ctypes.POINTER(vp)]
+    lib.ugo_fec_stream_tx_destroy.argtypes = [vp]
+    lib.ugo_fec_stream_tx_destroy.restype = None
+    lib.ugo_fec_stream_tx_window.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(sz)]
+    lib.ugo_fec_stream_tx_queue.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(sz)]
+    lib.ugo_fec_stream_tx_set_create.argtypes = [vp, vp, sz, ctypes.POINTER(vp)]
+    lib.ugo_fec_stream_tx_set_destroy.argtypes = [vp]
+    lib.ugo_fec_stream_tx_set_destroy.restype = None
+    lib.ugo_fec_stream_tx_set_write.argtypes = [vp, vp, vp, vp, vp, vp]
+    lib.ugo_fec_stream_tx_set_release.argtypes = [vp, vp, vp]
+    lib.ugo_fec_stream_tx_set_retransmit.argtypes = [vp, vp, vp, vp, sz, vp, vp]
+    lib.ugo_fec_stream_tx_set_plan.argtypes = [vp, vp, sz, sz, sz, vp, vp, vp, vp, vp, vp, vp]
+    lib.ugo_fec_stream_tx_set_encode.argtypes = [vp, vp, vp, sz, vp, sz, vp, sz, vp, u, vp, sz, vp, vp, vp]
+    lib.ugo_fec_stream_tx_set_state.argtypes = [vp, vp]
     lib.ugo_fec_reconstruct_rows.argtypes = [vp, vp, vp, sz, sz, vp, sz, sz, u, vp, vp]
     lib.ugo_fec_lossy_groups.argtypes = [vp, vp, sz, u, vp, vp, vp]
     lib.ugo_fec_rx_recover_host.argtypes = [vp, vp, sz, vp, sz, vp, ctypes.c_uint64, sz, sz, vp, vp, vp, sz, sz, vp,
@@ -917,6 +946,215 @@ class StreamRxSet:
         """The members' records (STREAM_STATE_DTYPE [nconn]); waits for the last call on the set."""
         out = np.zeros(self.nconn, STREAM_STATE_DTYPE)
         _raise(load_library().ugo_fec_stream_set_state(self._h, out.ctypes.data))
+        return out
+
+
+class StreamTx:
+    """A connection's send window on the GPU (include/ugo_stream.h, send
+    windows): its unsent and unacknowledged stream bytes and its retransmission
+    queue.  Every call goes through a StreamTxSet; a set of one is the
+    single-connection form."""
+
+    def __init__(self, enc: Encoder, window_bytes: int, rq_cap: int = 64, start_offset: int = 0,
+                 start_packet_number: int = 0):
+        self.check_create(window_bytes, rq_cap)
+        h = ctypes.c_void_p()
+        _raise(load_library().ugo_fec_stream_tx_create(enc._h, window_bytes, rq_cap, start_offset,
+                                                       start_packet_number, ctypes.byref(h)))
+        self._h, self._enc = h, enc  # the context must outlive the window
+        self.window_bytes, self.rq_cap = window_bytes, rq_cap
+        self.device = enc.device
+
+    @staticmethod
+    def check_create(window_bytes: int, rq_cap: int):
+        _require(STREAM_MIN_WINDOW <= window_bytes <= STREAM_TX_MAX_WINDOW and window_bytes & (window_bytes - 1) == 0,
+                 f"window_bytes must be a power of two in [{STREAM_MIN_WINDOW}, 2^31]")
+        _require(1 <= rq_cap <= 1 << 24, "rq_cap must be in [1, 2^24]")
+
+    def close(self):
+        if getattr(self, "_h", None):
+            load_library().ugo_fec_stream_tx_destroy(self._h)
+            self._h = None
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def window(self):
+        """The window as a uint8 CUDA tensor [window_bytes] over the device memory
+        itself (stream byte x at index x & (window_bytes - 1))."""
+        p, n = ctypes.c_void_p(), ctypes.c_size_t()
+        _raise(load_library().ugo_fec_stream_tx_window(self._h, ctypes.byref(p), ctypes.byref(n)))
+        return torch.as_tensor(_DeviceBytes(p.value, n.value, self), device=torch.device("cuda", self.device))
+
+    def queue(self):
+        """The retransmission ring as a uint8 CUDA tensor [rq_cap, 16] over the
+        device memory itself (view on the host with STREAM_TX_RQ_DTYPE)."""
+        p, n = ctypes.c_void_p(), ctypes.c_size_t()
+        _raise(load_library().ugo_fec_stream_tx_queue(self._h, ctypes.byref(p), ctypes.byref(n)))
+        t = torch.as_tensor(_DeviceBytes(p.value, n.value * 16, self), device=torch.device("cuda", self.device))
+        return t.view(n.value, 16)
+
+
+class StreamTxSet:
+    """An ordered set of send windows (ugo_fec_stream_tx_set_*): write, plan and
+    encode for all of them per call, release and retransmit for what ARQ on the
+    host decides.  Per-connection operands are tensors of nconn elements in
+    device or pinned host memory.  Nothing is synchronised but states().  The
+    set does not own its members; close it before them."""
+
+    def __init__(self, enc: Encoder, txs):
+        txs = list(txs)
+        self.check_members(enc, txs)
+        arr = (ctypes.c_void_p * len(txs))(*[tx._h.value for tx in txs])
+        h = ctypes.c_void_p()
+        _raise(load_library().ugo_fec_stream_tx_set_create(enc._h, ctypes.addressof(arr), len(txs), ctypes.byref(h)))
+        self._h, self._enc, self.txs = h, enc, txs
+        self.nconn = len(txs)
+        self.device = enc.device
+
+    @staticmethod
+    def check_members(enc, txs):
+        _require(0 < len(txs) <= STREAM_SET_MAX_CONN, f"a set holds 1 to {STREAM_SET_MAX_CONN} windows")
+        _require(all(isinstance(tx, StreamTx) and getattr(tx, "_h", None) for tx in txs), "members must be open StreamTx")
+        _require(all(tx._enc is enc for tx in txs), "every member must belong to the set's context")
+        _require(len({id(tx) for tx in txs}) == len(txs), "a window may be listed once")
+
+    @staticmethod
+    def check_plan(max_payload: int, max_segments: int, max_packets: int):
+        _require(16 <= max_payload <= 0xffff, "max_payload must be in [16, 0xffff]")
+        _require(1 <= max_segments <= 0xffff, "max_segments must be in [1, 0xffff]")
+        _require(0 <= max_packets <= 1 << 31, "max_packets must be at most 2^31")
+
+    def check_per_conn(self, t, element_size: int, name: str):
+        _require(t.is_contiguous() and t.element_size() == element_size and t.numel() == self.nconn and
+                 not t.dtype.is_floating_point, f"{name} must be nconn contiguous {8 * element_size}-bit integers")
+
+    @staticmethod
+    def _check_list(t, m: int, element_size: int, name: str):
+        _require(t.is_contiguous() and t.element_size() == element_size and t.numel() == m and
+                 not t.dtype.is_floating_point, f"{name} must be {m} contiguous {8 * element_size}-bit integers")
+
+    def close(self):
+        if getattr(self, "_h", None):
+            load_library().ugo_fec_stream_tx_set_destroy(self._h)
+            self._h = None
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def write(self, src, src_off, n, n_written=None, stream=None):
+        """Conn.Write that never waits: n[c] bytes from src[src_off[c]:] (uint8,
+        any alignment; int64 [nconn] both) to member c, as many as its window
+        has room for.  Returns n_written int64 [nconn]."""
+        _require(src.is_contiguous() and src.element_size() == 1)
+        self.check_per_conn(src_off, 8, "src_off")
+        self.check_per_conn(n, 8, "n")
+        if n_written is None:
+            n_written = torch.zeros(self.nconn, dtype=torch.int64, device=torch.device("cuda", self.device))
+        self.check_per_conn(n_written, 8, "n_written")
+        _raise(load_library().ugo_fec_stream_tx_set_write(self._h, src.data_ptr(), src_off.data_ptr(), n.data_ptr(),
+                                                          n_written.data_ptr(), _stream_handle(stream)))
+        return n_written
+
+    def release(self, upto, stream=None):
+        """The peer acknowledged everything below upto[c] (int64 [nconn])."""
+        self.check_per_conn(upto, 8, "upto")
+        _raise(load_library().ugo_fec_stream_tx_set_release(self._h, upto.data_ptr(), _stream_handle(stream)))
+
+    def retransmit(self, conn_of, offset, length, status=None, stream=None):
+        """Queue segments for retransmission: conn_of int32 [m] (non-decreasing),
+        offset int64 [m], length int32 [m].  Returns status uint8 [m] of
+        STREAM_TX_RQ_*."""
+        m = conn_of.numel()
+        self._check_list(conn_of, m, 4, "conn_of")
+        self._check_list(offset, m, 8, "offset")
+        self._check_list(length, m, 4, "length")
+        if status is None:
+            status = torch.zeros(m, dtype=torch.uint8, device=torch.device("cuda", self.device))
+        self._check_list(status, m, 1, "status")
+        _raise(load_library().ugo_fec_stream_tx_set_retransmit(
+            self._h, conn_of.data_ptr(), offset.data_ptr(), length.data_ptr(), m, status.data_ptr(),
+            _stream_handle(stream)))
+        return status
+
+    def plan(self, budget, max_packets: int, max_payload: int = 1436, max_segments: int = 8, out=None, stream=None):
+        """The loop of Conn.sendPacket for every member (THE RULE of
+        include/ugo_stream.h): budget int32 [nconn] packets at the most per
+        member.  Returns (info uint8 [max_packets, 64], segs uint8 [max_packets,
+        max_segments, 16], conn_of int32 [max_packets], first_packet int64
+        [nconn], n_packets int32 [nconn], total int64 [1]); out = such a tuple
+        to reuse."""
+        self.check_plan(max_payload, max_segments, max_packets)
+        self.check_per_conn(budget, 4, "budget")
+        dev = torch.device("cuda", self.device)
+        if out is None:
+            out = (torch.zeros((max_packets, 64), dtype=torch.uint8, device=dev),
+                   torch.zeros((max_packets, max_segments, 16), dtype=torch.uint8, device=dev),
+                   torch.zeros(max_packets, dtype=torch.int32, device=dev),
+                   torch.zeros(self.nconn, dtype=torch.int64, device=dev),
+                   torch.zeros(self.nconn, dtype=torch.int32, device=dev),
+                   torch.zeros(1, dtype=torch.int64, device=dev))
+        info, segs, conn_of, first_packet, n_packets, total = out
+        _require(info.is_contiguous() and info.element_size() == 1 and tuple(info.shape) == (max_packets, 64))
+        _require(segs.is_contiguous() and segs.element_size() == 1 and
+                 tuple(segs.shape) == (max_packets, max_segments, 16))
+        self._check_list(conn_of, max_packets, 4, "conn_of")
+        self.check_per_conn(first_packet, 8, "first_packet")
+        self.check_per_conn(n_packets, 4, "n_packets")
+        self._check_list(total, 1, 8, "total")
+        _raise(load_library().ugo_fec_stream_tx_set_plan(
+            self._h, budget.data_ptr(), max_payload, max_segments, max_packets, info.data_ptr(), segs.data_ptr(),
+            conn_of.data_ptr(), first_packet.data_ptr(), n_packets.data_ptr(), total.data_ptr(),
+            _stream_handle(stream)))
+        return out
+
+    def encode(self, info, ranges, segs, conn_of, slot: int, npackets: Optional[int] = None, pad=None,
+               framed: bool = False, stream=None, out=None):
+        """Encoder.packet_encode with the segment bytes read from the members'
+        windows: conn_of int32 [>= npackets] names packet i's member.  npackets
+        defaults to info.shape[0]; the arrays may be longer (plan's
+        max_packets).  Returns (wire uint8 [npackets, slot], wire_lens int16,
+        status uint8)."""
+        npk = info.shape[0] if npackets is None else npackets
+        _require(0 <= npk <= info.shape[0])
+        _require(info.is_contiguous() and info.element_size() == 1 and info.dim() == 2 and info.shape[1] == 64)
+        _require(ranges.is_contiguous() and ranges.element_size() == 8 and ranges.dim() == 3 and
+                 ranges.shape[0] >= npk and ranges.shape[2] == 2)
+        _require(segs.is_contiguous() and segs.element_size() == 1 and segs.dim() == 3 and segs.shape[0] >= npk and
+                 segs.shape[2] == 16)
+        _require(conn_of.is_contiguous() and conn_of.element_size() == 4 and conn_of.numel() >= npk and
+                 not conn_of.dtype.is_floating_point)
+        _require(not (framed and pad is not None), "framed packets are encrypted by tx_assemble: pad must be None")
+        _require(slot % 16 == 0 and 0 < slot <= 0xffff, "slot must be a multiple of 16, at most 0xffff")
+        if pad is not None:
+            _require(pad.is_contiguous() and pad.element_size() == 1 and pad.numel() >= slot)
+        if out is not None:
+            wire, wire_lens, status = out
+            _require(wire.dim() == 2 and wire.shape[0] >= npk and wire.shape[1] == slot and wire.is_contiguous() and
+                     wire.element_size() == 1)
+            _require(wire_lens.numel() >= npk and wire_lens.element_size() == 2 and wire_lens.is_contiguous())
+            _require(status.numel() >= npk and status.element_size() == 1 and status.is_contiguous())
+        else:
+            dev = info.device
+            wire = torch.zeros((npk, slot), dtype=torch.uint8, device=dev)
+            wire_lens = torch.zeros(npk, dtype=torch.int16, device=dev)
+            status = torch.zeros(npk, dtype=torch.uint8, device=dev)
+        _raise(load_library().ugo_fec_stream_tx_set_encode(
+            self._h, info.data_ptr(), ranges.data_ptr(), ranges.shape[1], segs.data_ptr(), segs.shape[1],
+            conn_of.data_ptr(), npk, None if pad is None else pad.data_ptr(), PKT_FEC_FRAMED if framed else 0,
+            wire.data_ptr(), slot, wire_lens.data_ptr(), status.data_ptr(), _stream_handle(stream)))
+        return wire, wire_lens, status
+
+    def states(self) -> np.ndarray:
+        """The members' records (STREAM_TX_STATE_DTYPE [nconn]); waits for the last call on the set."""
+        out = np.zeros(self.nconn, STREAM_TX_STATE_DTYPE)
+        _raise(load_library().ugo_fec_stream_tx_set_state(self._h, out.ctypes.data))
         return out
 
 

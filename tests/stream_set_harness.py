@@ -53,15 +53,15 @@ def demux_deliver(rules, packets, conn_of, count_contested=True):
 
 
 # The per-connection grid sizes of a set, restated from stream_set_wblocks /
-# stream_set_rblocks (ugo_amd/csrc/stream_set_kernels.hip).  Used only to assert
+# stream_set_rblocks (ugo_amd/csrc/stream_kernels.hip).  Used only to assert
 # that a test's shape reaches the branch it names; not an oracle for the device.
 def expected_wblocks(max_cap):
-    """Blocks per connection of k_set_apply / k_set_scan: four bitmap words a thread."""
+    """Blocks per connection of k_apply<Many> / k_scan<Many>: four bitmap words a thread."""
     return max(1, min(-(-max_cap // 65536), 1024))
 
 
 def expected_rblocks(max_cap, nconn):
-    """Blocks per connection of k_set_read: four 16-B chunks a thread, the grid near 4,096 blocks."""
+    """Blocks per connection of k_read<Many>: four 16-B chunks a thread, the grid near 4,096 blocks."""
     by_window = -(-max_cap // 16384)
     by_grid = 1 if nconn >= 4096 else 4096 // nconn
     return max(1, min(by_window, by_grid, 2048))

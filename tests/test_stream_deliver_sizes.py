@@ -541,7 +541,7 @@ def test_ordered_pass_over_three_tiles(enc, pad_bytes, case, max_segments, statu
 # E. grid-stride passes, large reads
 E_CAP = 1 << 25
 E_RP = 1003
-E_B1 = (E_RP & ~63) + 64 * 1024 * 256     # where the second pass of k_stream_apply / k_stream_scan starts
+E_B1 = (E_RP & ~63) + 64 * 1024 * 256     # where the second pass of k_apply<One> / k_scan<One> starts
 E_B2 = E_CAP                              # the ring's physical end
 
 
@@ -581,7 +581,7 @@ def test_grid_stride_passes_and_large_reads(enc, pad_bytes):
     got = h.deliver(fill[::-1], data_off=lambda i, j: 1 + i % 15, slot=MAX_SLOT)
     assert (got == ACCEPTED).all() and h.rule.contested == 0
     assert h.rule.readable == E_B2 + 141 - E_RP >= (20 << 20) and h.rule.ngaps == 2
-    h.read(h.rule.readable - 100, dst_shift=3)                     # four passes of k_stream_read, across the end
+    h.read(h.rule.readable - 100, dst_shift=3)                     # four passes of k_read<One>, across the end
     assert h.rule.read_pos == E_B2 + 41 > E_B2                     # the one call went past the ring's end
     h.read(10000, dst_shift=9)
     assert h.rule.readable == 0

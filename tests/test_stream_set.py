@@ -416,6 +416,26 @@ def test_set_read_in_one_call(enc, pad_bytes):
 
 
 @pytest.mark.gpu
+def test_a_zero_length_read_at_the_end_of_stream_single_and_set(enc, pad_bytes):
+    """readable == 0 with the empty segment at read_pos.  The two entry points
+    differ on purpose: ugo_fec_stream_read with n == 0 still reports end of
+    stream, as RuleRx.read(0) does; ugo_fec_stream_set_read skips a member with
+    n[c] == 0 -- n_read 0, eof 0 -- and leaves its record bit for bit."""
+    rng = np.random.default_rng(111)
+    h = SetHarness(enc, [4096], slot=256, max_segments=2, pad=pad_bytes)
+    h.deliver([Packet([Seg(0, _bytes(rng, 100)), Seg(100)])], [0])
+    assert h.read([100])[0][1]                                         # everything read: end of stream
+    rule = h.rules[0]
+    assert rule.readable == 0 and rule.eof and rule.read(0) == (b"", True)
+    before = h.set.states()[0].tobytes()
+    s = Harness(enc, 4096, slot=256, max_segments=2, pad=pad_bytes, rx=h.rxs[0], rule=rule, ordered=h.ordered[0])
+    assert s.read(0) == (b"", True)            # Harness.read holds n_read and eof against the rule's
+    assert h.read([0])[0] == (b"", False)      # SetHarness.read holds them against the skip: 0 and 0
+    assert h.set.states()[0].tobytes() == before
+    h.close()
+
+
+@pytest.mark.gpu
 def test_set_argument_checks_against_a_context(enc):
     lib = fec.load_library()
     other = fec.New(4, 2, device=0)

@@ -1,7 +1,7 @@
 """Receive-window sets (ugo_fec_stream_set_*, include/ugo_stream.h) at the
 launch shapes that test_stream_set.py does not reach: several blocks per
-connection in k_set_read (ticket, scan_head, the split copy), in k_set_apply and
-k_set_scan (runs across the seam between two blocks' bitmap words, the first
+connection in k_read<Many> (ticket, scan_head, the split copy), in k_apply<Many> and
+k_scan<Many> (runs across the seam between two blocks' bitmap words, the first
 uncovered byte found by a later block, a wrapped window), members of very
 different sizes in one set, the ordered pass over an unaligned status array with
 three segment slots per packet, a member across 2^32 beside one at 0, lying
@@ -113,7 +113,7 @@ def _top_up(h, rng, c, upto):
 def reads_history(h, rng):
     """Group A over member 0 (the large one); the small members are read, or
     skipped with n == 0, in the same calls.  Copy seams between the blocks of
-    k_set_read lie every 4096 bytes from 16 * c0, c0 = (read_pos + 15) >> 4;
+    k_read<Many> lie every 4096 bytes from 16 * c0, c0 = (read_pos + 15) >> 4;
     block b of rblocks clears bitmap words [256 b, 256 b + 256) from read_pos &
     ~63 in its first pass.  Returns the blocks whose words held a head segment's
     start bit."""
@@ -232,7 +232,7 @@ def scan_start(h, rng, start):
 
 
 def scan_runs_history(h, rng, start):
-    """Uncovered runs at the seams between the blocks of k_set_scan: block b of
+    """Uncovered runs at the seams between the blocks of k_scan<Many>: block b of
     16 scans words 256 b + t + 4096 j from read_pos & ~63, so the seams lie every
     16,384 bytes from there.  Returns the holes."""
     r, cap = h.rules[0], h.caps[0]
@@ -584,7 +584,7 @@ def test_demultiplexing_raw_descriptors_agrees_with_hand_split():
 @pytest.mark.parametrize("name", list(READ_SETS))
 def test_reads_with_several_blocks_per_connection(enc, pad_bytes, name):
     """reads_history on the device: every length, seam, partly read head,
-    back-to-back pair and the end of stream, in sets whose k_set_read runs 2, 64
+    back-to-back pair and the end of stream, in sets whose k_read<Many> runs 2, 64
     and 256 blocks per connection."""
     caps = READ_SETS[name]
     assert expected_rblocks(max(caps), len(caps)) == READ_BLOCKS[name] >= 2

@@ -1,10 +1,11 @@
-// stream_device.hpp -- device helpers of stream delivery that the
-// single-connection kernels (stream_kernels.hip) and the receive-window-set
-// kernels (stream_set_kernels.hip) share: the statuses between the kernels of
-// a call, the clamped segment, the bitmap word arithmetic, one segment of the
-// ordered pass and the realigning copy of one segment.  Everything here works
-// on a StreamArgs, one connection's view of a batch; the set kernels build one
-// per packet from their table entry.  Device code only: include from a .hip
+// stream_device.hpp -- device helpers of the stream-delivery kernels
+// (stream_kernels.hip): the statuses between the kernels of a call, the clamped
+// segment, the bitmap word arithmetic, one segment of the ordered pass and the
+// realigning copy of one segment.  The helpers that need the batch take it as
+// `b` (pkts, pad, info, segs, seg_status, slot, max_segments: StreamArgs and
+// StreamSetArgs name these alike) and the connection as `e` (win, C, S, claim,
+// cont, rec, cap: StreamArgs itself for the single entry points, a
+// StreamSetEntry for a member of a set).  Device code only: include from a .hip
 // file, after stream_kernels.hpp.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -46,17 +47,21 @@ struct Seg {
   uint32_t data_off, len, avail;
 };
 
-__device__ __forceinline__ Seg to_seg(const StreamArgs& a, const ugo_pkt_segment& s) {
+template <class B>
+__device__ __forceinline__ Seg to_seg(const B& b, const ugo_pkt_segment& s) {
   Seg r;
   r.o = s.offset;
   r.data_off = s.data_off;
   r.len = s.len;
   uint32_t av = s.avail < s.len ? s.avail : s.len;
-  const u64 room = s.data_off < a.slot ? a.slot - s.data_off : 0;  // never read past the slot
+  const u64 room = s.data_off < b.slot ? b.slot - s.data_off : 0;  // never read past the slot
   r.avail = av < room ? av : static_cast<uint32_t>(room);
   return r;
 }
-__device__ __forceinline__ Seg load_seg(const StreamArgs& a, u64 idx) { return to_seg(a, a.segs[idx]); }
+template <class B>
+__device__ __forceinline__ Seg load_seg(const B& b, u64 idx) {
+  return to_seg(b, b.segs[idx]);
+}
 
 // The word that holds stream positions [p, p + 64) (p a multiple of 64): the
 // bits of [max(p, lo), min(p + 64, e)).  lo < p + 64 and e > p.
@@ -80,20 +85,22 @@ __device__ __forceinline__ bool group_any(bool v) {
   return ((b >> (g * kGroupLanes)) & ((1u << kGroupLanes) - 1u)) != 0;
 }
 
-__device__ __forceinline__ uint32_t nseg_of(const StreamArgs& a, u64 i) {
-  const uint32_t n = a.info[i].n_segments;
-  return n < a.max_segments ? n : a.max_segments;
+template <class B>
+__device__ __forceinline__ uint32_t nseg_of(const B& b, u64 i) {
+  const uint32_t n = b.info[i].n_segments;
+  return n < b.max_segments ? n : b.max_segments;
 }
 
 // --------------------------------------------------------------- ordered pass
 // One contested segment, by the 64 lanes of wave 0: steps 2-7 of the rule
 // against the bitmaps as they are now.  Reads and writes go to L2 (atomics), and
 // a fence ends each segment, so the next one sees this one's bits.
-__device__ bool ordered_one(const StreamArgs& a, u64 idx, uint32_t lane, u64 rp, u64 head, bool hv) {
-  const u64 cap = a.cap;
-  const Seg s = load_seg(a, idx);
+template <class B, class E>
+__device__ bool ordered_one(const B& b, const E& e, u64 idx, uint32_t lane, u64 rp, u64 head, bool hv) {
+  const u64 cap = e.cap;
+  const Seg s = load_seg(b, idx);
   const bool indom = s.o >= rp && s.o - rp < cap;
-  u64* sw = a.S + widx(s.o, cap);
+  u64* sw = e.S + widx(s.o, cap);
   const u64 sbit = 1ull << (s.o & 63);
   uint32_t res;
   if ((hv && s.o == head) || (indom && (aload(sw) & sbit))) {
@@ -102,11 +109,11 @@ __device__ bool ordered_one(const StreamArgs& a, u64 idx, uint32_t lane, u64 rp,
     if (lane == 0) atomicOr(sw, sbit);
     res = kAccepted;
   } else {
-    const u64 e = s.o + s.len, lo = s.o > rp ? s.o : rp;
-    const u64 p0 = lo & ~63ull, nw = words_of(lo, e);
+    const u64 e2 = s.o + s.len, lo = s.o > rp ? s.o : rp;
+    const u64 p0 = lo & ~63ull, nw = words_of(lo, e2);
     bool anyc = s.o < rp, anyu = false;
     for (u64 k = lane; k < nw; k += 64) {
-      const u64 p = p0 + 64 * k, m = range_mask(p, lo, e), w = aload(a.C + widx(p, cap));
+      const u64 p = p0 + 64 * k, m = range_mask(p, lo, e2), w = aload(e.C + widx(p, cap));
       anyc |= (w & m) != 0;
       anyu |= (~w & m) != 0;
     }
@@ -115,7 +122,7 @@ __device__ bool ordered_one(const StreamArgs& a, u64 idx, uint32_t lane, u64 rp,
     if (!anyc) {
       for (u64 k = lane; k < nw; k += 64) {
         const u64 p = p0 + 64 * k;
-        atomicOr(a.C + widx(p, cap), range_mask(p, lo, e));
+        atomicOr(e.C + widx(p, cap), range_mask(p, lo, e2));
       }
       if (lane == 0) atomicOr(sw, sbit);
       res = kAccepted;
@@ -124,22 +131,22 @@ __device__ bool ordered_one(const StreamArgs& a, u64 idx, uint32_t lane, u64 rp,
     } else {
       res = kOverlap;
       if (lane == 0) {
-        a.rec->pub.err = UGO_STREAM_OVERLAP;
-        a.rec->pub.err_packet = idx / a.max_segments;
-        a.rec->pub.err_segment = static_cast<uint32_t>(idx % a.max_segments);
-        a.rec->fatal_idx = idx;
+        e.rec->pub.err = UGO_STREAM_OVERLAP;
+        e.rec->pub.err_packet = idx / b.max_segments;
+        e.rec->pub.err_segment = static_cast<uint32_t>(idx % b.max_segments);
+        e.rec->fatal_idx = idx;
       }
     }
   }
-  // its contested bits have served (k_stream_resolve read them)
+  // its contested bits have served (k_resolve read them)
   if (s.len == 0) {
-    if (lane == 0) *(a.cont + widx(s.o, cap)) = 0;
+    if (lane == 0) *(e.cont + widx(s.o, cap)) = 0;
   } else {
-    const u64 e = s.o + s.len, lo = s.o > rp ? s.o : rp;
-    const u64 p0 = lo & ~63ull, nw = words_of(lo, e);
-    for (u64 k = lane; k < nw; k += 64) a.cont[widx(p0 + 64 * k, cap)] = 0;
+    const u64 e2 = s.o + s.len, lo = s.o > rp ? s.o : rp;
+    const u64 p0 = lo & ~63ull, nw = words_of(lo, e2);
+    for (u64 k = lane; k < nw; k += 64) e.cont[widx(p0 + 64 * k, cap)] = 0;
   }
-  if (lane == 0) a.seg_status[idx] = static_cast<uint8_t>(res);
+  if (lane == 0) b.seg_status[idx] = static_cast<uint8_t>(res);
   __threadfence();
   return res == kOverlap;
 }
@@ -159,10 +166,11 @@ __device__ __forceinline__ uint32_t seg_byte(const uint8_t* src, const uint8_t* 
 // straddles the wrap): one unaligned 16-B load, the pad XOR, one aligned
 // nontemporal 16-B store.  The up-to-15 bytes on either side: byte stores, one
 // per lane.  No byte outside [o, o + len) is written.
-__device__ __forceinline__ void copy_segment(const StreamArgs& a, u64 i, const Seg& s, uint32_t hl) {
-  const uint8_t* src = a.pkts + i * a.slot + s.data_off;
-  const uint8_t* padp = a.pad ? a.pad + s.data_off : nullptr;
-  const u64 o = s.o, e = s.o + s.len, capm = a.cap - 1;
+template <class B>
+__device__ __forceinline__ void copy_segment(const B& b, uint8_t* win, u64 cap, u64 i, const Seg& s, uint32_t hl) {
+  const uint8_t* src = b.pkts + i * b.slot + s.data_off;
+  const uint8_t* padp = b.pad ? b.pad + s.data_off : nullptr;
+  const u64 o = s.o, e = s.o + s.len, capm = cap - 1;
   const u64 c0 = (o + 15) >> 4, c1 = e >> 4;  // whole chunks [c0, c1)
   for (u64 c = c0 + hl; c < c1; c += 4ull * kCopyLanes) {
     u32x4 v[4];
@@ -186,14 +194,14 @@ __device__ __forceinline__ void copy_segment(const StreamArgs& a, u64 i, const S
 #pragma unroll
     for (uint32_t q = 0; q < 4; ++q) {
       const u64 cc = c + q * kCopyLanes;
-      if (cc < c1) __builtin_nontemporal_store(v[q], reinterpret_cast<u32x4*>(a.win + ((16 * cc) & capm)));
+      if (cc < c1) __builtin_nontemporal_store(v[q], reinterpret_cast<u32x4*>(win + ((16 * cc) & capm)));
     }
   }
   const u64 head_end = e < 16 * c0 ? e : 16 * c0;                   // head bytes [o, head_end)
   const u64 tail_start = 16 * c1 > head_end ? 16 * c1 : head_end;  // tail bytes [tail_start, e)
   const u64 x = hl < 16 ? o + hl : tail_start + (hl - 16);
   if (hl < 16 ? x < head_end : x < e)
-    a.win[x & capm] = static_cast<uint8_t>(seg_byte(src, padp, static_cast<uint32_t>(x - o), s.avail));
+    win[x & capm] = static_cast<uint8_t>(seg_byte(src, padp, static_cast<uint32_t>(x - o), s.avail));
 }
 
 }  // namespace

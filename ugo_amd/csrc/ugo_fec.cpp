@@ -2244,6 +2244,48 @@ hipError_t stream_rx_sync_sets(ugo_stream_rx* rx) {
     if (set->used && e == hipSuccess) e = hipStreamSynchronize(set->last);
   return e;
 }
+
+// A window as the kernels take it: rx->bits holds C | S | claim | contested,
+// cap / 64 words each.
+ugo::kern::StreamSetEntry stream_rx_entry(const ugo_stream_rx* rx) {
+  const size_t words = rx->cap / 64;
+  return {rx->win, rx->bits, rx->bits + words, rx->bits + 2 * words, rx->bits + 3 * words, rx->rec, rx->cap};
+}
+
+// The batch of a deliver call; conn_of is the set form's and stays null for a
+// single window.
+struct StreamBatch {
+  const uint8_t* pkts;
+  size_t slot;
+  const uint8_t* pad;
+  const ugo_pkt_info* info;
+  const ugo_pkt_segment* segs;
+  size_t max_segments, npk;
+  const uint32_t* conn_of;
+  uint8_t* seg_status;
+};
+
+// What ugo_fec_stream_deliver and ugo_fec_stream_set_deliver do alike: the
+// argument checks, the device, the device views of the batch and the timer
+// around launch(b), which gets the batch with its pointers as the device sees
+// them.
+extern "C++" template <class Launch>
+int stream_deliver_call(ugo_fec* c, StreamBatch b, bool set, Launch launch) {
+  if (c->poisoned) return UGO_FEC_ERR_HIP;
+  if (b.npk == 0) return UGO_FEC_OK;
+  if (!b.pkts || !b.info || !b.segs || (set && !b.conn_of) || !b.seg_status || b.slot % 16 || b.slot == 0 ||
+      b.slot > 0xffff || reinterpret_cast<uintptr_t>(b.pkts) % 16 ||
+      (b.pad && reinterpret_cast<uintptr_t>(b.pad) % 16) || reinterpret_cast<uintptr_t>(b.conn_of) % 4 ||
+      b.max_segments == 0 || b.max_segments > 0xffff || b.npk > (size_t(1) << 31))
+    return UGO_FEC_ERR_INVALID_ARG;
+  DeviceGuard g(c->device);
+  if (!g.ok) return UGO_FEC_ERR_NO_DEVICE;
+  if (!device_view(b.pkts) || !device_view(b.pad) || !device_view(b.info) || !device_view(b.segs) ||
+      !device_view(b.conn_of) || !device_view(b.seg_status))
+    return UGO_FEC_ERR_INVALID_ARG;
+  TimerScope ts(c);
+  return hip_status(launch(b));
+}
 }  // namespace
 
 int ugo_fec_stream_rx_create(ugo_fec* c, size_t window_bytes, ugo_stream_rx** out) {
@@ -2294,38 +2336,28 @@ int ugo_fec_stream_deliver(ugo_stream_rx* rx, const uint8_t* pkts, size_t slot, 
                            const ugo_pkt_info* info, const ugo_pkt_segment* segs, size_t max_segments, size_t npk,
                            uint8_t* seg_status, void* stream) {
   if (!rx) return UGO_FEC_ERR_INVALID_ARG;
-  ugo_fec* c = rx->ctx;
-  if (c->poisoned) return UGO_FEC_ERR_HIP;
-  if (npk == 0) return UGO_FEC_OK;
-  if (!pkts || !info || !segs || !seg_status || slot % 16 || slot == 0 || slot > 0xffff ||
-      reinterpret_cast<uintptr_t>(pkts) % 16 || (pad && reinterpret_cast<uintptr_t>(pad) % 16) ||
-      max_segments == 0 || max_segments > 0xffff || npk > (size_t(1) << 31))
-    return UGO_FEC_ERR_INVALID_ARG;
-  DeviceGuard g(c->device);
-  if (!g.ok) return UGO_FEC_ERR_NO_DEVICE;
-  if (!device_view(pkts) || !device_view(pad) || !device_view(info) || !device_view(segs) ||
-      !device_view(seg_status))
-    return UGO_FEC_ERR_INVALID_ARG;
-  TimerScope ts(c);
-  const size_t words = rx->cap / 64;
-  ugo::kern::StreamArgs a{};
-  a.pkts = pkts;
-  a.pad = pad;
-  a.info = info;
-  a.segs = segs;
-  a.seg_status = seg_status;
-  a.win = rx->win;
-  a.C = rx->bits;
-  a.S = rx->bits + words;
-  a.claim = rx->bits + 2 * words;
-  a.cont = rx->bits + 3 * words;
-  a.rec = rx->rec;
-  a.npk = npk;
-  a.slot = slot;
-  a.cap = rx->cap;
-  a.max_segments = static_cast<uint32_t>(max_segments);
-  rx->last = static_cast<hipStream_t>(stream);
-  return hip_status(ugo::kern::launch_stream_deliver(a, rx->last));
+  const StreamBatch batch{pkts, slot, pad, info, segs, max_segments, npk, nullptr, seg_status};
+  return stream_deliver_call(rx->ctx, batch, false, [&](const StreamBatch& b) {
+    const ugo::kern::StreamSetEntry e = stream_rx_entry(rx);
+    ugo::kern::StreamArgs a{};
+    a.pkts = b.pkts;
+    a.pad = b.pad;
+    a.info = b.info;
+    a.segs = b.segs;
+    a.seg_status = b.seg_status;
+    a.win = e.win;
+    a.C = e.C;
+    a.S = e.S;
+    a.claim = e.claim;
+    a.cont = e.cont;
+    a.rec = e.rec;
+    a.npk = b.npk;
+    a.slot = b.slot;
+    a.cap = e.cap;
+    a.max_segments = static_cast<uint32_t>(b.max_segments);
+    rx->last = static_cast<hipStream_t>(stream);
+    return ugo::kern::launch_stream_deliver(a, rx->last);
+  });
 }
 
 int ugo_fec_stream_read(ugo_stream_rx* rx, uint8_t* dst, size_t n, uint64_t* n_read, uint8_t* eof, void* stream) {
@@ -2336,17 +2368,17 @@ int ugo_fec_stream_read(ugo_stream_rx* rx, uint8_t* dst, size_t n, uint64_t* n_r
   if (!g.ok) return UGO_FEC_ERR_NO_DEVICE;
   if (!device_view(dst) || !device_view(n_read) || !device_view(eof)) return UGO_FEC_ERR_INVALID_ARG;
   TimerScope ts(c);
-  const size_t words = rx->cap / 64;
+  const ugo::kern::StreamSetEntry e = stream_rx_entry(rx);
   ugo::kern::StreamReadArgs a{};
-  a.win = rx->win;
-  a.C = rx->bits;
-  a.S = rx->bits + words;
-  a.rec = rx->rec;
+  a.win = e.win;
+  a.C = e.C;
+  a.S = e.S;
+  a.rec = e.rec;
   a.dst = dst;
   a.n_read = reinterpret_cast<unsigned long long*>(n_read);
   a.eof = eof;
   a.n = n;
-  a.cap = rx->cap;
+  a.cap = e.cap;
   rx->last = static_cast<hipStream_t>(stream);
   return hip_status(ugo::kern::launch_stream_read(a, rx->last));
 }
@@ -2387,10 +2419,8 @@ int ugo_fec_stream_set_create(ugo_fec* c, ugo_stream_rx* const* rxs, size_t ncon
   std::vector<ugo::kern::StreamSetEntry> host(nconn);
   size_t max_cap = 0;
   for (size_t i = 0; i < nconn; ++i) {
-    ugo_stream_rx* rx = rxs[i];
-    const size_t words = rx->cap / 64;
-    host[i] = {rx->win, rx->bits, rx->bits + words, rx->bits + 2 * words, rx->bits + 3 * words, rx->rec, rx->cap};
-    max_cap = std::max(max_cap, rx->cap);
+    host[i] = stream_rx_entry(rxs[i]);
+    max_cap = std::max(max_cap, rxs[i]->cap);
   }
   set->wblocks = ugo::kern::stream_set_wblocks(max_cap);
   set->rblocks = ugo::kern::stream_set_rblocks(max_cap, static_cast<uint32_t>(nconn));
@@ -2424,36 +2454,25 @@ int ugo_fec_stream_set_deliver(ugo_stream_rx_set* set, const uint8_t* pkts, size
                                const ugo_pkt_info* info, const ugo_pkt_segment* segs, size_t max_segments,
                                size_t npk, const uint32_t* conn_of, uint8_t* seg_status, void* stream) {
   if (!set) return UGO_FEC_ERR_INVALID_ARG;
-  ugo_fec* c = set->ctx;
-  if (c->poisoned) return UGO_FEC_ERR_HIP;
-  if (npk == 0) return UGO_FEC_OK;
-  if (!pkts || !info || !segs || !conn_of || !seg_status || slot % 16 || slot == 0 || slot > 0xffff ||
-      reinterpret_cast<uintptr_t>(pkts) % 16 || (pad && reinterpret_cast<uintptr_t>(pad) % 16) ||
-      reinterpret_cast<uintptr_t>(conn_of) % 4 || max_segments == 0 || max_segments > 0xffff ||
-      npk > (size_t(1) << 31))
-    return UGO_FEC_ERR_INVALID_ARG;
-  DeviceGuard g(c->device);
-  if (!g.ok) return UGO_FEC_ERR_NO_DEVICE;
-  if (!device_view(pkts) || !device_view(pad) || !device_view(info) || !device_view(segs) ||
-      !device_view(conn_of) || !device_view(seg_status))
-    return UGO_FEC_ERR_INVALID_ARG;
-  TimerScope ts(c);
-  ugo::kern::StreamSetArgs a{};
-  a.pkts = pkts;
-  a.pad = pad;
-  a.info = info;
-  a.segs = segs;
-  a.seg_status = seg_status;
-  a.conn_of = conn_of;
-  a.table = set->table;
-  a.npk = npk;
-  a.slot = slot;
-  a.nconn = static_cast<uint32_t>(set->members.size());
-  a.max_segments = static_cast<uint32_t>(max_segments);
-  a.wblocks = set->wblocks;
-  set->last = static_cast<hipStream_t>(stream);
-  set->used = true;
-  return hip_status(ugo::kern::launch_stream_set_deliver(a, set->last));
+  const StreamBatch batch{pkts, slot, pad, info, segs, max_segments, npk, conn_of, seg_status};
+  return stream_deliver_call(set->ctx, batch, true, [&](const StreamBatch& b) {
+    ugo::kern::StreamSetArgs a{};
+    a.pkts = b.pkts;
+    a.pad = b.pad;
+    a.info = b.info;
+    a.segs = b.segs;
+    a.seg_status = b.seg_status;
+    a.conn_of = b.conn_of;
+    a.table = set->table;
+    a.npk = b.npk;
+    a.slot = b.slot;
+    a.nconn = static_cast<uint32_t>(set->members.size());
+    a.max_segments = static_cast<uint32_t>(b.max_segments);
+    a.wblocks = set->wblocks;
+    set->last = static_cast<hipStream_t>(stream);
+    set->used = true;
+    return ugo::kern::launch_stream_set_deliver(a, set->last);
+  });
 }
 
 int ugo_fec_stream_set_read(ugo_stream_rx_set* set, uint8_t* dst, const uint64_t* dst_off, const uint64_t* n,

@@ -66,7 +66,9 @@ extern "C" {
  *    UGO_FEC_KERNEL_PACKET_ENCODE; the ugo_fec_stream_* entry points with
  *    ugo_stream_status (ugo_stream.h), UGO_FEC_KERNEL_STREAM_DELIVER and
  *    UGO_FEC_KERNEL_STREAM_READ; the send windows, ugo_fec_stream_tx_*
- *    (ugo_stream.h), with UGO_PKT_OUT_OF_WINDOW and UGO_FEC_KERNEL_STREAM_TX. */
+ *    (ugo_stream.h), with UGO_PKT_OUT_OF_WINDOW and UGO_FEC_KERNEL_STREAM_TX;
+ *    the receive histories, ugo_fec_ack_* (ugo_ack.h), with UGO_FEC_KERNEL_ACK
+ *    (12, defined there). */
 #define UGO_FEC_ABI_VERSION 9
 
 /* Status codes.  1..5 map 1:1 onto the klauspost/reedsolomon error values

@@ -1,0 +1,314 @@
+"""CPU statements of the receiver's acknowledgement state (include/ugo_ack.h);
+test infrastructure only, written from the Go text.
+
+GoHistory    recvHistory (ugo/recv_history.go:24-117): the interval list.
+GoReceiver   packetReceiver (ugo/packet_receiver.go:39-170): receivedPacket,
+             receivedStopWaiting, buildSack, gcReceivedTimes, as they stand,
+             bugs included.  Two flags say when the reference has left the
+             ground the rule shares with it: hit_a (the walk of :69-75 stepped
+             over a missing number and went on counting, deviation (a)) and
+             hit_b (largestObserved fell below largestInOrderObserved,
+             deviation (b)).
+RuleAck      THE RULE of the header: one receive history with its ring bitmap,
+             receive in phases, the SACK of attach.
+receive_set / attach_set   what a set call means for a list of RuleAck.
+"""
+import numpy as np
+
+PKT_OK = 0
+STREAM_OUT_OF_WINDOW = 3
+MAX_OUTSTANDING = 1000
+TOO_MANY_OUTSTANDING = 1
+NOT_ATTACHED, ATTACHED, TRUNCATED = 0, 1, 2
+
+errTimeLost = "packetReceiver: packet time lost"
+errInvalidPacketNumber = "packetReceiver: Invalid packet number"
+errTooManyOutstandingReceivedPackets = "packetReceiver: Too Many Outstanding Received Packets"
+
+
+# ---------------------------------------------------------------- the reference
+class GoHistory:
+    """utils.PacketIntervalList as a Python list of [Start, End], front first."""
+
+    def __init__(self):
+        self.ranges = []
+
+    def receivedPacket(self, p):
+        r = self.ranges
+        if not r:
+            r.append([p, p])
+            if p != 1:
+                r.insert(0, [0, 0])
+            return
+        k = len(r) - 1
+        while k >= 0:
+            el = r[k]
+            if el[0] <= p <= el[1]:
+                return
+            extended = False
+            if el[1] == p - 1:
+                extended, el[1] = True, p
+            elif el[0] == p + 1:
+                extended, el[0] = True, p
+            if extended:
+                if k > 0 and r[k - 1][1] + 1 == el[0]:
+                    r[k - 1][1] = el[1]
+                    del r[k]
+                return
+            if p > el[1]:
+                r.insert(k + 1, [p, p])
+                return
+            k -= 1
+        r.insert(0, [p, p])
+
+    def deleteBelow(self, leastUnacked):
+        r = self.ranges
+        k = 0
+        while k < len(r):
+            el = r[k]
+            if el[0] <= leastUnacked <= el[1]:
+                el[0] = leastUnacked
+            if el[1] < leastUnacked:
+                del r[k]                       # r[k] is now the next element
+                if k < len(r) and r[k][0] > leastUnacked:
+                    r.insert(k, [leastUnacked, leastUnacked])
+                    k += 1                     # go on with that next element
+                elif k == len(r):
+                    r.append([leastUnacked, leastUnacked])
+                    return
+            else:
+                return
+
+    def getAckRanges(self):
+        return [(el[0], el[1]) for el in reversed(self.ranges)]
+
+
+class GoReceiver:
+    def __init__(self):
+        self.largestInOrderObserved = 0
+        self.largestObserved = 0
+        self.ignorePacketsBelow = 0
+        self.currentSack = None
+        self.stateChanged = False
+        self.packetHistory = GoHistory()
+        self.receivedTimes = {}
+        self.lowestInReceivedTimes = 0
+        self.clock = 0
+        self.hit_a = self.hit_b = False
+
+    def receivedPacket(self, packetNumber):
+        if packetNumber == 0:
+            return errInvalidPacketNumber
+        if packetNumber <= self.ignorePacketsBelow:
+            return None
+        if packetNumber <= self.largestInOrderObserved or packetNumber in self.receivedTimes:
+            return None
+        self.packetHistory.receivedPacket(packetNumber)
+        self.stateChanged = True
+        self.currentSack = None
+        if packetNumber > self.largestObserved:
+            self.largestObserved = packetNumber
+        if packetNumber == self.largestInOrderObserved + 1:
+            self.largestInOrderObserved = packetNumber
+            self.receivedTimes.pop(self.largestInOrderObserved - 1, None)
+            missed = False
+            for i in range(self.largestInOrderObserved + 1, self.largestObserved + 1):
+                if i in self.receivedTimes:
+                    if missed:
+                        self.hit_a = True
+                    self.largestInOrderObserved += 1
+                    self.receivedTimes.pop(self.largestInOrderObserved - 1, None)
+                else:
+                    missed = True
+            self.packetHistory.deleteBelow(self.largestInOrderObserved)
+        self.clock += 1
+        self.receivedTimes[packetNumber] = self.clock
+        self.lowestInReceivedTimes = self.largestInOrderObserved
+        if len(self.receivedTimes) > 1000:
+            return errTooManyOutstandingReceivedPackets
+        return None
+
+    def receivedStopWaiting(self, stopWaiting):
+        if self.ignorePacketsBelow >= stopWaiting:
+            return None
+        self.ignorePacketsBelow = stopWaiting - 1
+        self.stateChanged = True
+        if stopWaiting > self.largestInOrderObserved:
+            self.largestInOrderObserved = stopWaiting - 1
+        for i in range(self.largestInOrderObserved + 1, self.largestObserved + 1):
+            if i in self.receivedTimes:
+                self.largestInOrderObserved = i
+                self.ignorePacketsBelow = i - 1
+            else:
+                break
+        self.packetHistory.deleteBelow(self.largestInOrderObserved)
+        self.gcReceivedTimes()
+        if self.largestObserved < self.largestInOrderObserved:
+            self.hit_b = True
+        return None
+
+    def gcReceivedTimes(self):
+        for i in range(self.lowestInReceivedTimes, self.ignorePacketsBelow + 1):
+            self.receivedTimes.pop(i, None)
+        self.lowestInReceivedTimes = self.ignorePacketsBelow
+
+    def buildSack(self, dequeue):
+        """(sack, err); sack = (largestAcked, largestInOrder, ackRanges or None)."""
+        if not self.stateChanged:
+            return None, None
+        if dequeue:
+            self.stateChanged = False
+        if self.currentSack is not None:
+            return self.currentSack, None
+        if self.largestObserved not in self.receivedTimes:
+            return None, errTimeLost
+        ackRanges = self.packetHistory.getAckRanges()
+        self.currentSack = (self.largestObserved, self.largestInOrderObserved,
+                            ackRanges if len(ackRanges) > 1 else None)
+        return self.currentSack, None
+
+    def handle(self, packetNumber, stopWaiting):
+        """The packetReceiver calls of Conn.handlePacket (ugo/conn.go:446-468)."""
+        if packetNumber != 0:
+            self.receivedPacket(packetNumber)
+        if stopWaiting != 0:
+            self.receivedStopWaiting(stopWaiting)
+
+    def view(self):
+        """What a SACK built now would say, and stateChanged."""
+        ackRanges = self.packetHistory.getAckRanges()
+        return (self.largestObserved, self.largestInOrderObserved, ackRanges if len(ackRanges) > 1 else [],
+                self.stateChanged)
+
+
+# ---------------------------------------------------------------- the rule
+class RuleAck:
+    FIELDS = ("largest_in_order", "largest_observed", "ignore_below", "lo_time_us", "fresh", "old", "out_of_window",
+              "outstanding", "changed", "err")
+
+    def __init__(self, wp=1024):
+        assert wp >= 1024 and wp & (wp - 1) == 0
+        self.wp = wp
+        self.S = set()                         # the numbers whose bit is set
+        self.lio = self.lo = self.ipb = self.lo_time_us = 0
+        self.fresh = self.old = self.out_of_window = 0
+        self.outstanding = self.changed = self.err = 0
+
+    def receive(self, pkts, now_us=0, filtered=0):
+        """pkts: [(packet_number, stop_waiting)] of the packets that take part,
+        filtered: how many more passed every test but seg_status."""
+        if self.err:
+            return
+        self.out_of_window += filtered
+        if not pkts:
+            return
+        lo_was = self.lo
+        m = max(sw for _, sw in pkts)
+        if m != 0 and m > self.ipb:                                   # 1. floor
+            self.ipb, self.changed = m - 1, 1
+            if m - 1 > self.lio:
+                self.lio = m - 1
+                self.S = {x for x in self.S if x > self.lio}
+        for n, _ in pkts:                                             # 2. packets
+            if n == 0:
+                continue
+            if n <= self.lio or n in self.S:
+                self.old += 1
+            elif n > self.lio + self.wp:
+                self.out_of_window += 1
+            else:
+                self.S.add(n)
+                self.fresh += 1
+                self.changed = 1
+                self.lo = max(self.lo, n)
+        while self.lio + 1 in self.S:                                 # 3. advance
+            self.lio += 1
+            self.S.discard(self.lio)
+        self.lo = max(self.lo, self.lio)
+        self.outstanding = len(self.S)
+        if self.lo > lo_was:
+            self.lo_time_us = now_us
+        if self.outstanding > MAX_OUTSTANDING:
+            self.err = TOO_MANY_OUTSTANDING
+
+    def touch(self):
+        self.changed = 1
+
+    def record(self):
+        return dict(largest_in_order=self.lio, largest_observed=self.lo, ignore_below=self.ipb,
+                    lo_time_us=self.lo_time_us, fresh=self.fresh, old=self.old, out_of_window=self.out_of_window,
+                    outstanding=self.outstanding, changed=self.changed, err=self.err)
+
+    def bitmap(self):
+        """The ring as the device holds it: uint64 [wp / 64]."""
+        B = np.zeros(self.wp // 64, np.uint64)
+        for n in self.S:
+            assert self.lio < n <= self.lio + self.wp
+            p = n & (self.wp - 1)
+            B[p >> 6] |= np.uint64(1 << (p & 63))
+        return B
+
+    def runs(self):
+        """Maximal runs of set bits, highest first, as (first, last)."""
+        out = []
+        for n in sorted(self.S, reverse=True):
+            if out and out[-1][0] == n + 1:
+                out[-1][0] = n
+            else:
+                out.append([n, n])
+        return [tuple(r) for r in out]
+
+    def view(self):
+        runs = self.runs()
+        return (self.lo, self.lio, runs + [(self.lio, self.lio)] if runs else [], bool(self.changed))
+
+    def sack(self, max_ranges):
+        """(largest_acked, n_ranges, rows, how) as attach writes them."""
+        runs = self.runs()
+        if not runs:
+            return self.lo, 0, [], ATTACHED
+        how = TRUNCATED if len(runs) + 1 > max_ranges else ATTACHED
+        if max_ranges < 2:
+            return self.lio, 0, [], how
+        rows = runs[:max_ranges - 1] + [(self.lio, self.lio)]
+        return self.lo, len(rows), rows, how
+
+
+def receive_set(rules, packets, now_us, max_segments=0):
+    """packets: [(status, conn_of, packet_number, stop_waiting, n_segments,
+    seg_status row or None)] in batch order."""
+    part = [[] for _ in rules]
+    filtered = [0] * len(rules)
+    for status, conn, n, sw, nseg, row in packets:
+        if status != PKT_OK or not 0 <= conn < len(rules) or rules[conn].err:
+            continue
+        if row is not None and STREAM_OUT_OF_WINDOW in list(row[:min(nseg, max_segments)]):
+            filtered[conn] += 1
+            continue
+        part[conn].append((n, sw))
+    for r, p, f in zip(rules, part, filtered):
+        r.receive(p, now_us, f)
+
+
+def attach_set(rules, now_us, first_packet, n_packets, total, may_ack_only, max_packets, max_ranges):
+    """Returns (writes, total_out, attached): writes = [(t, conn, ack_only,
+    largest_acked, largest_in_order, delay_us, n_ranges, rows)]; clears changed
+    for the attached members."""
+    writes, attached, k = [], [NOT_ATTACHED] * len(rules), 0
+    for c, r in enumerate(rules):
+        if not r.changed or r.err:
+            continue
+        t, ack_only = None, False
+        if n_packets[c] > 0:
+            t = first_packet[c]
+        elif may_ack_only is not None and may_ack_only[c]:
+            t, ack_only = total + k, True
+            k += 1
+        if t is None or t >= max_packets:
+            continue
+        la, nr, rows, how = r.sack(max_ranges)
+        writes.append((t, c, ack_only, la, r.lio, max(0, now_us - r.lo_time_us), nr, rows))
+        attached[c] = how
+        r.changed = 0
+    appended = sum(1 for w in writes if w[2])
+    return writes, total + appended, attached

@@ -1,0 +1,691 @@
+"""Receive histories (include/ugo_ack.h).
+
+CPU: THE RULE (tests/ack_ref.py, RuleAck) against a restatement of the
+reference's packetReceiver and recvHistory (GoReceiver) over two seeded
+families, the rule's independence of the order inside a call, one directed
+case per deviation, the record's layout and the argument errors that need no
+launch.
+
+GPU (-m gpu): the device against one RuleAck per member through
+tests/ack_harness.py, which compares after every call every record, every
+watched bitmap in whole and every output array in whole over sentinels.
+"""
+import ctypes
+import random
+import re
+
+import numpy as np
+import pytest
+
+import ack_ref as ar
+from ugo_amd import fec
+
+N_SEQ = 20000
+
+
+# ---------------------------------------------------------------- the two families
+def family_a(rng):
+    """Calls of 1-7 (packet_number, stop_waiting): numbers in order, some held
+    back and released later, the highest held first; uniform duplicates of
+    what was sent; stop-waitings from [1, largest observed].  The lowest
+    missing number is therefore the last of the missing to arrive, so the
+    reference's walk (deviation (a)) never has a hole to step over, and no
+    stop-waiting passes largestObserved (deviation (b))."""
+    next_n, held, sent, lo = 1, [], [], 0
+    hold_p = rng.choice((0.2, 0.4, 0.6))
+    calls = []
+    for _ in range(rng.randint(4, 12)):
+        call = []
+        while len(call) < rng.randint(1, 7):
+            r = rng.random()
+            if held and r < 0.2:
+                n = max(held)
+                held.remove(n)
+            elif sent and r < 0.3:
+                n = rng.choice(sent)
+            else:
+                n, next_n = next_n, next_n + 1
+                if rng.random() < hold_p:
+                    held.append(n)
+                    continue
+            sent.append(n)
+            lo = max(lo, n)
+            call.append((n, rng.randint(1, lo) if rng.random() < 0.15 else 0))
+        calls.append(call)
+    return calls
+
+
+def family_random(rng):
+    """Calls of 1-7 packets: mostly the next number, sometimes a jump of 2-3,
+    sometimes any number seen so far, now and then a pure ACK (number 0); a
+    stop-waiting in one packet of fourteen, drawn up to two past the top."""
+    top, calls = 0, []
+    for _ in range(rng.randint(3, 9)):
+        call = []
+        for _ in range(rng.randint(1, 7)):
+            r = rng.random()
+            if r < 0.55:
+                top += 1
+                n = top
+            elif r < 0.80:
+                top += rng.randint(2, 3)
+                n = top
+            elif r < 0.97:
+                n = rng.randint(1, top + 1)
+                top = max(top, n)
+            else:
+                n = 0
+            call.append((n, rng.randint(1, top + 2) if rng.random() < 0.07 else 0))
+        calls.append(call)
+    return calls
+
+
+def run_reference(ref, call):
+    for n, sw in call:
+        ref.handle(n, sw)
+
+
+def test_family_a_equals_the_reference_after_every_call():
+    """20,000 sequences that meet neither deviation, no sequence left out.
+    After every call the reference's largestAcked, largestInOrder and ackRanges
+    equal the rule's and buildSack never fails.  stateChanged equals the
+    rule's changed but for one thing, which is asserted as exactly that: the
+    loop of receivedStopWaiting (:114-122) raises ignorePacketsBelow to
+    largestInOrderObserved - 1 as it advances, the advance of receivedPacket
+    does not, and the rule's ipb is m - 1 whichever of the two the order inside
+    the call would have made it.  So ipb <= ignorePacketsBelow always, and a
+    later stop-waiting in between sets changed here and not there: one more
+    ACK with the same content, never one fewer (deviation (e) of the header)."""
+    states = most_ranges = extra_states = 0
+    for seed in range(N_SEQ):
+        rng = random.Random(0xA000000 + seed)
+        ref, rule = ar.GoReceiver(), ar.RuleAck()
+        extra = False                                    # changed is up for a stop-waiting the reference ignored
+        for k, call in enumerate(family_a(rng)):
+            ref_ipb, rule_ipb = ref.ignorePacketsBelow, rule.ipb
+            run_reference(ref, call)
+            rule.receive(call, now_us=k)
+            assert not ref.hit_a and not ref.hit_b, (seed, k)
+            rv, uv = ref.view(), rule.view()
+            assert rv[:3] == uv[:3], (seed, k, call, rv, uv)
+            assert rule.ipb <= ref.ignorePacketsBelow, (seed, k)
+            extra = extra or any(rule_ipb < sw <= ref_ipb for _, sw in call)
+            assert uv[3] == (rv[3] or extra), (seed, k, call, rv, uv)
+            extra_states += uv[3] != rv[3]
+            sack, err = ref.buildSack(False)
+            assert err is None, (seed, k, err)
+            if k % 3 == 2:                               # an ACK goes out: both sides clear their flag
+                ref.buildSack(True)
+                rule.changed, extra = 0, False
+            states += 1
+            most_ranges = max(most_ranges, len(rule.view()[2]))
+    print(f"family A: {states} states compared, up to {most_ranges} ranges, "
+          f"{extra_states} with changed up for a stop-waiting the reference ignored")
+    assert most_ranges >= 8                              # the family reaches long range lists
+
+
+def test_random_family_equals_the_reference_up_to_a_deviation():
+    """20,000 random sequences, each compared up to the first call in which
+    the reference reaches deviation (a) or (b)."""
+    reached = states = with_ranges = 0
+    for seed in range(N_SEQ):
+        rng = random.Random(0xB000000 + seed)
+        ref, rule = ar.GoReceiver(), ar.RuleAck()
+        extra = False                                    # as in family A
+        for k, call in enumerate(family_random(rng)):
+            ref_ipb, rule_ipb = ref.ignorePacketsBelow, rule.ipb
+            run_reference(ref, call)
+            if ref.hit_a or ref.hit_b:
+                reached += 1
+                break
+            rule.receive(call, now_us=k)
+            rv, uv = ref.view(), rule.view()
+            assert rv[:3] == uv[:3], (seed, k, call, rv, uv)
+            assert rule.ipb <= ref.ignorePacketsBelow, (seed, k)
+            extra = extra or any(rule_ipb < sw <= ref_ipb for _, sw in call)
+            assert uv[3] == (rv[3] or extra), (seed, k, call, rv, uv)
+            if k % 3 == 2:
+                ref.buildSack(True)
+                rule.changed, extra = 0, False
+            states += 1
+            with_ranges += bool(uv[2])
+    print(f"random family: {reached / N_SEQ:.1%} of the sequences reach (a) or (b); "
+          f"{with_ranges / states:.1%} of {states} compared states carry ranges")
+    assert reached <= 0.40 * N_SEQ
+    assert with_ranges >= 0.25 * states
+
+
+ORDER_FREE = ("largest_in_order", "largest_observed", "ignore_below", "lo_time_us", "outstanding", "changed", "err")
+
+
+def test_per_packet_and_phased_forms_agree():
+    """The rule applied packet by packet in arrival order and the rule applied
+    in phases per call: the same bitmap, the same lio, lo, ipb, lo_time_us,
+    outstanding, changed and err, and the same number of packets counted, for
+    random splits into calls of 1-7 packets.  How the counted packets divide
+    into fresh and old may differ (a number the call's own floor passes is
+    fresh packet by packet and old in phases), which the header says."""
+    split_differs = 0
+    for seed in range(N_SEQ):
+        rng = random.Random(0xC000000 + seed)
+        calls = family_random(rng) if seed & 1 else family_a(rng)
+        phased, single = ar.RuleAck(), ar.RuleAck()
+        for k, call in enumerate(calls):
+            phased.receive(call, now_us=k + 1)
+            for p in call:
+                single.receive([p], now_us=k + 1)
+            a, b = phased.record(), single.record()
+            assert phased.S == single.S and all(a[f] == b[f] for f in ORDER_FREE), (seed, k, a, b)
+            assert a["fresh"] + a["old"] + a["out_of_window"] == b["fresh"] + b["old"] + b["out_of_window"]
+            assert a["out_of_window"] == b["out_of_window"] == 0
+        split_differs += phased.fresh != single.fresh
+    print(f"fresh/old split differs in {split_differs} of {N_SEQ} sequences")
+
+
+def test_order_inside_a_call_does_not_matter():
+    for seed in range(2000):
+        rng = random.Random(0xD000000 + seed)
+        one, two = ar.RuleAck(), ar.RuleAck()
+        for k, call in enumerate(family_random(rng)):
+            shuffled = list(call)
+            rng.shuffle(shuffled)
+            one.receive(call, now_us=k)
+            two.receive(shuffled, now_us=k)
+            assert one.record() == two.record() and one.S == two.S, (seed, k)
+
+
+# ---------------------------------------------------------------- the deviations, one case each
+def test_deviation_a_two_holes():
+    ref, rule = ar.GoReceiver(), ar.RuleAck()
+    for n in (1, 3, 5, 2):
+        ref.handle(n, 0)
+        rule.receive([(n, 0)])
+    assert ref.hit_a and ref.largestInOrderObserved == 4          # packet 4 never arrived
+    assert ref.view()[2] == [(5, 5), (4, 4)]                      # ... and the SACK acknowledges it
+    assert (rule.lio, rule.lo, rule.view()[2]) == (3, 5, [(5, 5), (3, 3)])
+
+
+def test_deviation_b_stop_waiting_past_largest_observed():
+    ref, rule = ar.GoReceiver(), ar.RuleAck()
+    for p in ((1, 0), (2, 0), (0, 6)):
+        ref.handle(*p)
+        rule.receive([p])
+    assert ref.hit_b and (ref.largestObserved, ref.largestInOrderObserved) == (2, 5)
+    assert ref.buildSack(False) == (None, ar.errTimeLost)         # sendPacket would fail the connection
+    assert (rule.lio, rule.lo, rule.ipb, rule.changed) == (5, 5, 5, 1) and rule.view()[2] == []
+
+
+def test_deviation_c_window_bound():
+    rule = ar.RuleAck(1024)
+    rule.receive([(1, 0), (1024, 0), (1025, 0)])                  # judged against lio as the call found it
+    assert (rule.lio, rule.lo, rule.fresh, rule.out_of_window) == (1, 1024, 2, 1) and rule.S == {1024}
+
+
+def test_deviation_d_phase_order_and_error_after_the_call():
+    rule = ar.RuleAck()
+    rule.receive([(3, 0), (0, 5)])                                # the floor of the call comes first: 3 is old
+    assert (rule.lio, rule.fresh, rule.old, rule.changed) == (4, 0, 1, 1)
+    phased, single = ar.RuleAck(1024), ar.RuleAck(1024)           # the window bound is judged behind the floor
+    phased.receive([(1100, 0), (0, 100)])
+    for p in ((1100, 0), (0, 100)):
+        single.receive([p])
+    assert (phased.S, phased.lo, phased.out_of_window) == ({1100}, 1100, 0)
+    assert (single.S, single.lo, single.out_of_window) == (set(), 99, 1)
+    call = [(2 * k + 2, 0) for k in range(1001)] + [(1, 0)]
+    single = ar.RuleAck(2048)
+    for p in call:
+        single.receive([p])
+    assert single.err == ar.TOO_MANY_OUTSTANDING and single.lio == 0   # the transient the batch does not see
+    rule = ar.RuleAck(2048)
+    rule.receive(call)                                            # 1,001 apart; 1 and 2 then join
+    assert rule.outstanding == 1000 and rule.err == 0             # judged on what is left after the call
+    rule.receive([(2 * 1001 + 2, 0)])
+    assert rule.outstanding == 1001 and rule.err == ar.TOO_MANY_OUTSTANDING
+    before = rule.record()
+    rule.receive([(3, 0)])                                        # inert from then on
+    assert rule.record() == before
+
+
+# ---------------------------------------------------------------- layout and arguments
+def test_record_layout_and_constants():
+    d = fec.ACK_STATE_DTYPE
+    assert d.itemsize == 64 and d.names[:10] == ar.RuleAck.FIELDS
+    assert [d.fields[n][1] for n in d.names] == [0, 8, 16, 24, 32, 40, 48, 56, 60, 61, 62]
+    src = open(fec.ACK_HEADER_PATH).read()
+    assert re.search(r"#define UGO_FEC_KERNEL_ACK 12\b", src)
+    assert fec.KERNEL_NAMES[12] == "ack" and fec.KERNEL_IDS["ack"] == 12
+    assert re.search(r"#define UGO_ACK_MAX_OUTSTANDING 1000u", src) and fec.ACK_MAX_OUTSTANDING == ar.MAX_OUTSTANDING
+    assert (fec.ACK_NOT_ATTACHED, fec.ACK_ATTACHED, fec.ACK_TRUNCATED) == (ar.NOT_ATTACHED, ar.ATTACHED, ar.TRUNCATED)
+    assert fec.STREAM_OUT_OF_WINDOW == ar.STREAM_OUT_OF_WINDOW and fec.ACK_TOO_MANY_OUTSTANDING == 1
+
+
+def test_symbols_are_exported_within_abi_9():
+    lib = fec.load_library()
+    names = [s for s in fec.header_symbols() if s.startswith("ugo_fec_ack_")]
+    assert sorted(names) == ["ugo_fec_ack_rx_bitmap", "ugo_fec_ack_rx_create", "ugo_fec_ack_rx_destroy",
+                             "ugo_fec_ack_rx_state", "ugo_fec_ack_set_attach", "ugo_fec_ack_set_create",
+                             "ugo_fec_ack_set_destroy", "ugo_fec_ack_set_receive", "ugo_fec_ack_set_state",
+                             "ugo_fec_ack_set_touch"]
+    for s in names:
+        assert hasattr(lib, s), s
+    assert lib.ugo_fec_abi_version() == 9
+
+
+def test_argument_errors_that_need_no_launch():
+    lib = fec.load_library()
+    h = ctypes.c_void_p(1)
+    assert lib.ugo_fec_ack_rx_create(None, 1024, ctypes.byref(h)) == 6 and h.value is None
+    assert lib.ugo_fec_ack_rx_create(None, 1024, None) == 6
+    assert lib.ugo_fec_ack_rx_state(None, None) == 6
+    assert lib.ugo_fec_ack_rx_bitmap(None, None, None) == 6
+    h = ctypes.c_void_p(1)
+    assert lib.ugo_fec_ack_set_create(None, None, 1, ctypes.byref(h)) == 6 and h.value is None
+    assert lib.ugo_fec_ack_set_receive(None, None, None, 1, None, 0, 0, None) == 6
+    assert lib.ugo_fec_ack_set_touch(None, None, None) == 6
+    assert lib.ugo_fec_ack_set_attach(None, 0, None, None, None, None, 0, None, None, 0, None, None, None, None) == 6
+    assert lib.ugo_fec_ack_set_state(None, None) == 6
+    lib.ugo_fec_ack_rx_destroy(None)
+    lib.ugo_fec_ack_set_destroy(None)
+    for wp in (0, 512, 1023, 1536, (1 << 20) + 1, 1 << 21):
+        with pytest.raises(ValueError):
+            fec.AckRx.check_window(wp)
+    for wp in (1024, 4096, 1 << 20):
+        fec.AckRx.check_window(wp)
+    with pytest.raises(ValueError):
+        fec.AckRxSet.check_members(None, [])
+
+
+# ---------------------------------------------------------------- GPU
+import torch  # noqa: E402
+
+import packet_ref as pr  # noqa: E402,F401
+from ack_harness import NO_CONN, AckHarness, _put  # noqa: E402
+
+KEY = b"\x0f\x1e\x2d\x3c\x4b\x5a\x69\x78"
+
+
+@pytest.fixture(scope="module")
+def enc(gpu):
+    return fec.New(10, 3)
+
+
+def P(conn, n, sw=0, status=0, nseg=0):
+    return (status, conn, n, sw, nseg)
+
+
+def plan_like(counts):
+    """first_packet / total as set_plan leaves them for these n_packets."""
+    first, cur = [], 0
+    for k in counts:
+        first.append(cur)
+        cur += k
+    return first, cur
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("wp", [1024, 4096, 8192])
+def test_runs_wrap_and_whole_window(enc, wp):
+    """Wp = a quarter of a wave's words, exactly one pass of the advance, two
+    passes.  lio & (Wp-1) = Wp-2, so lio+1 is the ring's last bit and lio+2 its
+    first: runs that end at bit 63 of a word, cross a word boundary and cross
+    the ring's wrap; lio+Wp is recorded and lio+Wp+1 is not; then the whole
+    window in one call."""
+    h = AckHarness(enc, [wp])
+    lio = 5 * wp + wp - 2
+    h.adopt(0, lio)
+    bits = [0, 1] + list(range(10, 64)) + list(range(126, 130)) + [wp - 3, wp - 2]   # ring bit b is number lio+2+b
+    pk = [P(0, lio + 2 + b) for b in bits] + [P(0, lio + wp + 1)]
+    st = h.receive(pk)
+    assert (st["fresh"][0], st["out_of_window"][0], st["largest_observed"][0]) == (len(bits), 1, lio + wp)
+    assert h.rules[0].runs() == [(lio + wp - 1, lio + wp), (lio + 128, lio + 131), (lio + 12, lio + 65),
+                                 (lio + 2, lio + 3)]
+    w = h.attach([0], [1], 1, 2, 8)[0]
+    assert w[0][6] == 5
+    st = h.receive([P(0, lio + 1), P(0, lio + 2)])                 # the advance crosses the wrap
+    assert (st["largest_in_order"][0], st["old"][0], st["outstanding"][0]) == (lio + 3, 1, len(bits) - 2)
+    lio += 3
+    st = h.receive([P(0, lio + k) for k in range(wp, 0, -1)])      # everything up to lio + Wp, highest first
+    assert (st["largest_in_order"][0], st["outstanding"][0], st["err"][0]) == (lio + wp, 0, 0)
+    assert h.attach([0], [0], 0, 1, 4, may=[1])[0][0][6] == 0      # no run: n_ranges 0
+    h.close()
+
+
+@pytest.mark.gpu
+def test_floor_inside_a_word_and_past_the_window(enc):
+    h = AckHarness(enc, [1024, 4096])
+    h.receive([P(c, n) for c in (0, 1) for n in (3, 4, 5, 20, 21, 40, 70, 900)])
+    st = h.receive([P(0, 0, sw=21), P(1, 22, sw=5), P(1, 0, sw=4)])  # member 0: 20 cleared, 21 joins lio
+    assert st["largest_in_order"].tolist() == [21, 5] and st["ignore_below"].tolist() == [20, 4]
+    assert st["outstanding"].tolist() == [3, 6]
+    st = h.receive([P(0, 0, sw=21), P(1, 0, sw=3)])                  # m = ipb + 1 is taken again, m <= ipb is not
+    assert st["changed"].tolist() == [1, 1]
+    h.attach([0, 0], [0, 0], 0, 2, 8, may=[1, 1])
+    st = h.receive([P(0, 0, sw=21), P(1, 0, sw=3)])
+    assert st["changed"].tolist() == [1, 0]
+    st = h.receive([P(0, 5000, sw=3000), P(1, 0, sw=4096 + 5 + 900)])  # past lio + Wp: everything cleared
+    assert st["largest_in_order"].tolist() == [2999, 5000] and st["outstanding"].tolist() == [0, 0]
+    assert st["out_of_window"].tolist() == [1, 0] and st["largest_observed"].tolist() == [2999, 5000]
+    h.close()
+
+
+@pytest.mark.gpu
+def test_packet_numbers_across_2_32(enc):
+    h = AckHarness(enc, [1024, 2048])
+    h.adopt(0, (1 << 32) - 5)
+    nums = [(1 << 32) + d for d in (-3, -2, -1, 0, 1, 5, 6, 900)]
+    st = h.receive([P(0, n) for n in nums] + [P(1, 7)])
+    assert st["largest_observed"].tolist() == [(1 << 32) + 900, 7]
+    w = h.attach([0, 1], [1, 1], 2, 4, 6)[0]
+    assert w[0][7] == [((1 << 32) + 900,) * 2, ((1 << 32) + 5, (1 << 32) + 6), ((1 << 32) - 3, (1 << 32) + 1),
+                       ((1 << 32) - 5,) * 2]
+    st = h.receive([P(0, (1 << 32) - 4), P(0, (1 << 32) + 2, sw=(1 << 32) + 4)])
+    assert st["largest_in_order"][0] == (1 << 32) + 3 and st["outstanding"][0] == 3
+    h.close()
+
+
+@pytest.mark.gpu
+def test_one_number_in_different_waves_and_blocks(enc):
+    """Copies of one fresh number in one call of 3,500 packets, which is four
+    blocks of the kernel that places the bits (1,024 packets each) and
+    fourteen of the one before it (256): two lanes of a wave, another wave,
+    and every block.  fresh is exactly 1 per member.  Block 1 begins with
+    member 1 and block 2 with member 0, so their copies there are counted
+    through the block's own counters; blocks 0 and 3 begin with no connection,
+    so the copies there are added to the member's counters directly."""
+    h = AckHarness(enc, [1024, 1024])
+    pk = [P(NO_CONN, 9)] * 3500
+    for i in (3, 17, 70, 300, 1024, 1500, 2100, 3499):
+        pk[i] = P(1, 9)
+    for i in (500, 2048, 2500, 3100):
+        pk[i] = P(0, 9)
+    st = h.receive(pk)
+    assert st["fresh"].tolist() == [1, 1] and st["old"].tolist() == [3, 7]
+    assert st["largest_observed"].tolist() == [9, 9] and st["outstanding"].tolist() == [1, 1]
+    st = h.receive(pk)                                             # and again, all of them old now
+    assert st["fresh"].tolist() == [1, 1] and st["old"].tolist() == [7, 15]
+    h.close()
+
+
+@pytest.mark.gpu
+def test_one_member_100000_in_order_packets(enc):
+    """The contended shape: every wave lands on one or two words of one bitmap."""
+    wp, n = 1 << 17, 100000
+    h = AckHarness(enc, [wp])
+    st = h.receive([P(0, k) for k in range(1, n + 1)])
+    assert (st["largest_in_order"][0], st["fresh"][0], st["outstanding"][0]) == (n, n, 0)
+    st = h.receive([P(0, k) for k in range(n + 2, n + 702)] + [P(0, n)] * 3)
+    assert (st["largest_in_order"][0], st["outstanding"][0], st["old"][0]) == (n, 700, 3)
+    h.close()
+
+
+@pytest.mark.gpu
+def test_conn_of_alternating_lane_by_lane(enc):
+    rng = random.Random(5)
+    h = AckHarness(enc, [1024, 4096, 8192])
+    for call in range(3):
+        pk = []
+        for i in range(777):
+            c = i % 3
+            pk.append(P(c, 1 + call * 200 + rng.randrange(260), sw=rng.randrange(call * 200 + 1) if i % 97 == 0 else 0))
+        h.receive(pk)
+    assert all(r.outstanding > 0 and r.old > 0 for r in h.rules)
+    h.close()
+
+
+@pytest.mark.gpu
+def test_participation_filters(enc):
+    OOW = fec.STREAM_OUT_OF_WINDOW
+    h = AckHarness(enc, [1024, 1024])
+    pk = [P(NO_CONN, 1, sw=9), P(2, 1, sw=9), P(0x80000000, 2), P(0x7fffffff, 3)]          # no connection
+    pk += [P(0, 10 + s, sw=20, status=s) for s in range(1, 11)]                             # not OK
+    st = h.receive(pk)
+    assert all(r.record() == ar.RuleAck().record() for r in h.rules) and not st["changed"].any()
+    st = h.receive([P(1, 0, sw=4), P(0, 0)])                                                # a pure ACK, a stop-waiting alone
+    assert st["largest_in_order"].tolist() == [0, 3] and st["changed"].tolist() == [0, 1]
+    # seg_status: three entries per packet, one byte off alignment
+    pk = [P(0, 1, nseg=3), P(0, 2, sw=50, nseg=3), P(0, 3, nseg=1), P(0, 4, nseg=7), P(0, 5, nseg=7), P(0, 6, nseg=0),
+          P(1, 7, nseg=2), P(NO_CONN, 8, nseg=3), P(1, 9, nseg=3, status=2)]
+    rows = [[1, 1, 1], [1, 2, OOW], [1, OOW, OOW], [1, 1, OOW], [2, 2, 2], [OOW, OOW, OOW], [OOW, 1, 1], [OOW] * 3,
+            [OOW] * 3]
+    st = h.receive(pk, seg_rows=rows, max_segments=3, seg_shift=1)
+    assert st["out_of_window"].tolist() == [2, 1] and st["fresh"].tolist() == [4, 0]
+    assert st["largest_in_order"].tolist() == [1, 3] and st["ignore_below"].tolist() == [0, 3]  # sw = 50 ignored
+    only = [P(1, 30, nseg=1)]
+    st = h.receive(only, seg_rows=[[OOW, 0]], max_segments=2)       # nothing but the count changes
+    assert st["out_of_window"].tolist() == [2, 2] and st["lo_time_us"][1] == h.rules[1].lo_time_us
+    h.close()
+
+
+@pytest.mark.gpu
+def test_outstanding_limit_and_an_inert_member(enc):
+    h = AckHarness(enc, [4096, 4096, 4096])
+    st = h.receive([P(c, 2 * k + 2) for k in range(1000) for c in (0, 1, 2)])
+    assert st["outstanding"].tolist() == [1000] * 3 and not st["err"].any()
+    st = h.receive([P(1, 2002), P(0, 1)])
+    assert st["outstanding"].tolist() == [999, 1001, 1000] and st["err"].tolist() == [0, 1, 0]
+    before = h.rxs[1].state().tobytes()
+    st = h.receive([P(1, 1, sw=900), P(0, 3), P(2, 1, sw=7), P(1, 3000)],
+                   seg_rows=[[3], [0], [0], [3]], max_segments=1)
+    assert h.rxs[1].state().tobytes() == before and st["largest_in_order"].tolist() == [4, 0, 6]
+    h.touch([0, 1, 0])
+    w, _, _, _, total_out, att = h.attach([0, 0, 0], [0, 0, 0], 0, 3, 4, may=[1, 1, 1])
+    assert att == [2, 0, 2] and total_out == 2 and [x[1] for x in w] == [0, 2]
+    h.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("nconn", [3, 1025, 32769])
+def test_many_members(enc, nconn):
+    """Sets of one scan block, of two, and of more than 32 with a third level
+    of nothing: mixed windows, every member's record, the ACK-only slots in set
+    order and the clamp at max_packets inside the members."""
+    rng = random.Random(nconn)
+    wps = [(1024, 4096, 8192)[c % 3] for c in range(nconn)]
+    h = AckHarness(enc, wps, watch=[0, 1, 2, nconn - 1, nconn // 2])
+    pk = []
+    for c in range(nconn):
+        if c % 5 != 4:                                             # every fifth member stays idle
+            pk += [P(c, 1), P(c, 3 + c % 7)] if c % 2 else [P(c, 1), P(c, 2)]
+    rng.shuffle(pk)
+    h.receive(pk)
+    counts = [1 if c % 3 == 0 else 0 for c in range(nconn)]
+    first, total = plan_like(counts)
+    may = [0 if c % 11 == 0 else 1 for c in range(nconn)]
+    want = sum(1 for c in range(nconn) if c % 5 != 4 and counts[c] == 0 and may[c])
+    max_packets = total + want - want // 3                          # the last third of the slots does not exist
+    w, _, _, _, total_out, att = h.attach(first, counts, total, max_packets, 3, may=may)
+    assert total_out == max_packets and sum(1 for x in w if x[2]) == want - want // 3
+    assert att.count(0) >= nconn // 5 and h.rules[1].changed == 0
+    st = h.receive([P(nconn - 1, 2), P(0, 9)])
+    assert st["changed"][0] == 1
+    h.close()
+
+
+@pytest.mark.gpu
+def test_attach_cases(enc):
+    h = AckHarness(enc, [1024] * 6)
+    h.receive([P(c, n) for c in range(6) for n in (1, 3, 5, 6, 9)], now_us=500)     # three runs each
+    # runs + 1 = max_ranges, may_ack_only NULL, n_packets mixed
+    w, iv, rg, _, total_out, att = h.attach([0, 2, 2, 3, 3, 3], [2, 0, 1, 0, 0, 4], 7, 9, 4, now_us=800)
+    assert att == [1, 0, 1, 0, 0, 1] and total_out == 7 and [x[0] for x in w] == [0, 2, 3]
+    assert w[0][5] == 300 and w[0][7] == [(9, 9), (5, 6), (3, 3), (1, 1)]
+    st = h.set.states()
+    assert st["changed"].tolist() == [0, 1, 0, 1, 1, 0]
+    # one more run than the row holds; delay_us saturates; total_out on top of total
+    h.receive([P(c, 12) for c in range(6)], now_us=900)
+    w, iv, rg, _, total_out, att = h.attach([0] * 6, [0] * 6, 4, 8, 4, may=[1, 1, 0, 1, 1, 1], now_us=100,
+                                            alias_total=True)
+    assert att == [2, 2, 0, 2, 2, 0] and total_out == 8 and [x[0] for x in w] == [4, 5, 6, 7]   # member 5 clamped
+    assert w[0][5] == 0 and w[0][7] == [(12, 12), (9, 9), (5, 6), (1, 1)] and w[0][3] == 12
+    # max_ranges 1 and 0: nothing above lio is acknowledged
+    w, iv, rg, _, _, att = h.attach([0] * 6, [0] * 6, 0, 6, 1, may=[0, 0, 1, 0, 0, 1])
+    assert att == [0, 0, 2, 0, 0, 2] and [(x[3], x[6]) for x in w] == [(1, 0), (1, 0)]
+    h.touch([1, 0, 0, 0, 0, 0])
+    w, iv, rg, _, _, att = h.attach([3, 0, 0, 0, 0, 0], [1, 0, 0, 0, 0, 0], 4, 4, 0)
+    assert att == [2, 0, 0, 0, 0, 0] and (w[0][0], w[0][3], w[0][6]) == (3, 1, 0)
+    # first_packet past max_packets is clamped, an unchanged member gets nothing
+    h.touch([1, 0, 0, 0, 0, 0])
+    _, _, _, _, _, att = h.attach([9, 0, 0, 0, 0, 0], [1, 1, 1, 1, 1, 1], 6, 6, 8)
+    assert att == [0] * 6 and h.rules[0].changed == 1
+    h.close()
+
+
+@pytest.mark.gpu
+def test_pinned_operands_and_kernel_class(enc):
+    h = AckHarness(enc, [1024, 8192])
+    enc.timing_begin(32)
+    try:
+        h.receive([P(0, 1), P(1, 2), P(1, 4, nseg=1)], seg_rows=[[0], [0], [1]], max_segments=1, where="pinned")
+        h.touch([1, 0], where="pinned")
+        h.attach([0, 0], [0, 1], 1, 3, 4, may=[1, 1], where="pinned")
+    finally:
+        recs, untimed = enc.timing_end()
+    assert untimed == 0 and fec.KERNEL_IDS["ack"] == 12
+    # receive: 4 launches, touch 1, attach 3 (the state gather is not a timed call)
+    assert recs["kernel"].tolist() == [12] * (4 + 1 + 3)
+    h.close()
+
+
+@pytest.mark.gpu
+def test_argument_errors_on_the_device(enc):
+    """INVALID_ARG before any launch, with nothing written: pageable operands,
+    a member listed twice, a seg_status without max_segments, caps too large."""
+    lib = fec.load_library()
+    bad = fec.ErrInvalidArg.code
+    h = AckHarness(enc, [1024, 1024])
+    h.receive([P(0, 2), P(1, 2)])
+    out_set = ctypes.c_void_p(1)
+    twice = (ctypes.c_void_p * 2)(h.rxs[0]._h.value, h.rxs[0]._h.value)
+    assert lib.ugo_fec_ack_set_create(enc._h, ctypes.addressof(twice), 2, ctypes.byref(out_set)) == bad
+    assert out_set.value is None
+    with pytest.raises(ValueError):
+        fec.AckRxSet(enc, [h.rxs[0], h.rxs[0]])
+    out_rx = ctypes.c_void_p(1)
+    assert lib.ugo_fec_ack_rx_create(enc._h, 1000, ctypes.byref(out_rx)) == bad and out_rx.value is None
+    info = _put(np.zeros((4, 64), np.uint8))
+    conn = torch.zeros(4, dtype=torch.int32, device="cuda")
+    seg = torch.zeros(4, dtype=torch.uint8, device="cuda")
+    recv = lambda i, c, n, s, ms: lib.ugo_fec_ack_set_receive(h.set._h, i, c, n, s, ms, 5, None)  # noqa: E731
+    assert recv(torch.zeros((4, 64), dtype=torch.uint8).data_ptr(), conn.data_ptr(), 4, None, 0) == bad
+    assert recv(info.data_ptr(), torch.zeros(4, dtype=torch.int32).data_ptr(), 4, None, 0) == bad
+    assert recv(info.data_ptr(), conn.data_ptr(), 4, seg.data_ptr(), 0) == bad
+    assert recv(info.data_ptr(), conn.data_ptr(), 4, torch.zeros(4, dtype=torch.uint8).data_ptr(), 1) == bad
+    assert recv(info.data_ptr(), conn.data_ptr(), 4, None, 0x10000) == bad
+    assert recv(info.data_ptr() + 8, conn.data_ptr(), 3, None, 0) == bad
+    assert recv(None, conn.data_ptr(), 4, None, 0) == bad and recv(info.data_ptr(), None, 4, None, 0) == bad
+    assert recv(None, None, 0, None, 0) == 0                                           # an empty batch is a no-op
+    assert lib.ugo_fec_ack_set_touch(h.set._h, torch.zeros(2, dtype=torch.uint8).data_ptr(), None) == bad
+    buf = {k: torch.full((n,), 0x11, dtype=torch.uint8, device="cuda")
+           for k, n in (("first", 16), ("count", 8), ("total", 8), ("info", 256), ("ranges", 256), ("conn", 16),
+                        ("out", 8), ("att", 2))}
+
+    def attach(max_packets=4, max_ranges=4, **kw):
+        p = {k: v.data_ptr() for k, v in buf.items()}
+        p.update(kw)
+        return lib.ugo_fec_ack_set_attach(h.set._h, 9, p["first"], p["count"], p["total"], None, max_packets,
+                                          p["info"], p["ranges"], max_ranges, p["conn"], p["out"], p["att"], None)
+    assert attach(first=None) == bad and attach(count=None) == bad and attach(total=None) == bad
+    assert attach(info=None) == bad and attach(ranges=None) == bad and attach(conn=None) == bad
+    assert attach(out=None) == bad and attach(att=None) == bad
+    assert attach(max_ranges=0x10000) == bad and attach(max_packets=(1 << 31) + 1) == bad
+    assert attach(first=torch.zeros(2, dtype=torch.int64).data_ptr()) == bad           # pageable
+    assert attach(att=torch.zeros(2, dtype=torch.uint8).data_ptr()) == bad
+    torch.cuda.synchronize()
+    assert all(bool((t == 0x11).all()) for t in buf.values())
+    h.check()
+    h.close()
+
+
+@pytest.mark.gpu
+def test_round_trip_with_no_host_patch(enc):
+    """Three connections, nothing patched in by the host: write -> set_plan ->
+    ack attach -> set_encode -> tx_assemble -> rx_assemble (one packet dropped,
+    one repeated) -> packet_decode -> set_deliver + ack receive at the peer ->
+    attach onto the peer's plan -> set_encode -> packet_decode.  The decoded
+    SACK fields and ranges are the rule's, and the encoder accepts every
+    attached packet (its checks 7-9)."""
+    from stream_tx_harness import TxHarness
+    rng = np.random.default_rng(21)
+    d, n, S, slot, MR = 10, 13, 1470, 1488, 6
+    pad_bytes = fec.rc4_keystream(KEY, slot)
+    dpad = _put(np.frombuffer(pad_bytes, np.uint8)[:slot].copy())
+    # ---- side A: 20 packets (7 + 7 + 6), its own history has seen packets 1 and 3 of connection 2
+    A = TxHarness(enc, [16384] * 3, rq_caps=4)
+    ackA = AckHarness(enc, [1024] * 3)
+    ackA.receive([P(2, 1), P(2, 3)], now_us=10)
+    A.write([rng.integers(0, 256, k, dtype=np.uint8).tobytes() for k in (7 * 1432, 7 * 1432, 6 * 1432)])
+    a = A.plan([7, 7, 6], 20, max_segments=2)
+    assert a["count_np"] == [7, 7, 6]
+    rangesA = torch.zeros((20, MR, 2), dtype=torch.int64, device="cuda")
+    _, attA = ackA.set.attach(50, a["first"], a["count"], a["total"], a["info"], rangesA, a["conn"])
+    wA, _, attA_want = ar.attach_set(ackA.rules, 50, a["first_np"], a["count_np"], 20, None, 20, MR)
+    assert attA.tolist() == attA_want == [0, 0, 1]
+    wire_a, lens_a, st_a = A.set.encode(a["info"], rangesA, a["segs"], a["conn"], slot, npackets=20, framed=True)
+    assert not st_a.any()
+    G = 2
+    wire = torch.zeros((G * n, slot), dtype=torch.uint8, device="cuda")
+    wl = torch.zeros(G * n, dtype=torch.int16, device="cuda")
+    st = torch.full((G,), -1, dtype=torch.int8, device="cuda")
+    enc.tx_assemble(wire_a.contiguous(), lens_a, wire, wl, first_seq=0, pad=dpad, status=st)
+    assert st.tolist() == [0, 0]
+    # ---- the network: data packet 9 (connection 1's third) is lost, packet 4 arrives twice
+    lost, twice = 9, 4
+    wl_rx = wl.clone()
+    wl_rx[lost] = 0
+    wire_rx = torch.cat([wire, wire[twice:twice + 1]]).contiguous()
+    wl_rx = torch.cat([wl_rx, wl[twice:twice + 1]]).contiguous()
+    frames = torch.zeros((n, G, slot), dtype=torch.uint8, device="cuda")
+    present = torch.zeros(G, dtype=torch.int64, device="cuda")
+    stats = torch.zeros(5, dtype=torch.int32, device="cuda")
+    enc.rx_assemble(wire_rx, wl_rx, frames, present, shard_size=S, pad=dpad, frames=True, stats=stats)
+    assert present.tolist() == [((1 << n) - 1) & ~(1 << lost), (1 << n) - 1] and stats.tolist()[4] == 1
+    rows = frames[:d].reshape(d * G, slot)                      # row k * G + g is data packet g * d + k
+    order = np.array([g * d + k for k in range(d) for g in range(G)])
+    back = torch.from_numpy(np.argsort(order)).cuda()            # the packets in sending order
+    rl = wl_rx[:G * n].view(G, n)[:, :d].contiguous().view(-1)
+    info, ranges, segs = enc.packet_decode(rows[back].contiguous(), rl, framed=True, max_ranges=MR, max_segments=2)
+    I = info.cpu().numpy().view(fec.PKT_INFO_DTYPE).reshape(-1)
+    assert np.flatnonzero(I["status"]).tolist() == [lost]
+    first_of_2 = a["first_np"][2]
+    assert I["flags"][first_of_2] & 0x80 and (I["largest_acked"][first_of_2], I["n_ranges"][first_of_2]) == (3, 2)
+    assert ranges.cpu().numpy()[first_of_2, :2].tolist() == [[3, 3], [1, 1]]
+    # ---- side B: deliver, receive, and its own plan: connection 0 has data, 1 and 2 send an ACK alone
+    conn = a["conn"]
+    rxs = [fec.StreamRx(enc, 16384) for _ in range(3)]
+    rset = fec.StreamRxSet(enc, rxs)
+    seg_status = rset.deliver(rows[back].contiguous(), info, segs, conn)
+    ackB = AckHarness(enc, [1024, 4096, 1024])
+    ackB.set.receive(info, conn, 7000, seg_status=seg_status)
+    ar.receive_set(ackB.rules, [(int(I["status"][i]), int(a["conn_np"][i]), int(I["packet_number"][i]),
+                                 int(I["stop_waiting"][i]), int(I["n_segments"][i]), None) for i in range(20)], 7000)
+    stB = ackB.check()
+    assert stB["largest_in_order"].tolist() == [7, 2, 6] and stB["largest_observed"].tolist() == [7, 7, 6]
+    assert stB["outstanding"].tolist() == [0, 4, 0] and stB["changed"].tolist() == [1, 1, 1]
+    B = TxHarness(enc, [16384] * 3, rq_caps=4)
+    B.write([rng.integers(0, 256, 2000, dtype=np.uint8).tobytes(), b"", b""])
+    b = B.plan([4, 4, 4], 6, max_segments=2)
+    assert b["count_np"] == [2, 0, 0]
+    rangesB = torch.zeros((6, MR, 2), dtype=torch.int64, device="cuda")
+    may = _put(np.asarray([1, 1, 1], np.uint8))
+    total_out, attB = ackB.set.attach(7250, b["first"], b["count"], b["total"], b["info"], rangesB, b["conn"],
+                                      may_ack_only=may, total_out=b["total"])
+    wB, total_want, attB_want = ar.attach_set(ackB.rules, 7250, b["first_np"], b["count_np"], 2, [1, 1, 1], 6, MR)
+    ackB.check()
+    assert int(total_out.item()) == total_want == 4 and attB.tolist() == attB_want == [1, 1, 1]
+    wire_b, lens_b, st_b = B.set.encode(b["info"], rangesB, b["segs"], b["conn"], slot, npackets=4, pad=dpad)
+    assert not st_b.any() and (lens_b.cpu().numpy() > 0).all()
+    info2, ranges2, _ = enc.packet_decode(wire_b, lens_b, pad=dpad, max_ranges=MR, max_segments=2)
+    J = info2.cpu().numpy().view(fec.PKT_INFO_DTYPE).reshape(-1)
+    R = ranges2.cpu().numpy().view(np.uint64)
+    assert not J["status"].any() and J["flags"].tolist() == [0xA0, 0x20, 0x80, 0x80]
+    assert J["packet_number"].tolist() == [1, 2, 0, 0]
+    for t, c, ack_only, la, lio, delay, nr, rws in wB:
+        assert (J["largest_acked"][t], J["largest_in_order"][t], J["n_ranges"][t]) == (la, lio, nr), (t, c)
+        assert [tuple(x) for x in R[t, :nr].tolist()] == rws, (t, c)
+        assert abs(int(J["delay_us"][t]) - delay) <= delay // 64 + 1          # ufloat16 keeps 11 bits
+    assert [w[7] for w in wB] == [[], [(4, 7), (2, 2)], []]
+    rset.close()
+    for rx in rxs:
+        rx.close()
+    for x in (A, B, ackA, ackB):
+        x.close()

@@ -33,6 +33,8 @@
 #include "stream_kernels.hpp"
 #include "stream_set_kernels.hpp"
 #include "stream_tx_kernels.hpp"
+#include "ack_kernels.hpp"
+#include "host/ack_args.hpp"
 
 namespace {
 
@@ -2821,6 +2823,244 @@ int ugo_fec_stream_tx_set_state(ugo_stream_tx_set* set, ugo_stream_tx_state* hos
   if (!g.ok) return UGO_FEC_ERR_NO_DEVICE;
   const uint32_t nconn = static_cast<uint32_t>(set->members.size());
   if (ugo::kern::launch_stream_tx_gather(set->table, nconn, set->gathered, set->last) != hipSuccess ||
+      hipStreamSynchronize(set->last) != hipSuccess)
+    return UGO_FEC_ERR_HIP;
+  return hip_status(hipMemcpy(host_out, set->gathered, nconn * sizeof(*host_out), hipMemcpyDeviceToHost));
+}
+
+// ---------------------------------------------------------------- receive histories (include/ugo_ack.h)
+struct ugo_ack_rx {
+  ugo::ackargs::Member m{};             // ctx, bitmap, record, window: what a set's table is built from
+  ugo_fec* ctx = nullptr;
+  std::vector<ugo_ack_rx_set*> sets;    // the live sets it is a member of
+};
+
+struct ugo_ack_rx_set {
+  ugo_fec* ctx = nullptr;
+  std::vector<ugo_ack_rx*> members;
+  ugo::kern::AckEntry* table = nullptr;  // device, [nconn], uploaded once
+  ugo_ack_state* gathered = nullptr;     // device, [nconn], for ugo_fec_ack_set_state
+  ugo::kern::AckCall* call = nullptr;    // device, [nconn], zero between receive calls
+  uint32_t* slot_local = nullptr;        // device, [nconn]
+  uint64_t* words = nullptr;             // device: block_slots [kAckScanBlock] | total_in
+  hipStream_t last = nullptr;            // the stream of the last call on the set
+  bool used = false;
+};
+
+namespace {
+// prologue of every per-call entry point of a set of receive histories
+int ack_enter(ugo_ack_rx_set* set) {
+  if (!set) return UGO_FEC_ERR_INVALID_ARG;
+  if (set->ctx->poisoned) return UGO_FEC_ERR_HIP;
+  return UGO_FEC_OK;
+}
+}  // namespace
+
+int ugo_fec_ack_rx_create(ugo_fec* c, size_t window_packets, ugo_ack_rx** out) {
+  static_assert(sizeof(ugo_ack_state) == 64, "ugo_ack_state is 64 bytes");
+  static_assert(sizeof(ugo::kern::AckEntry) == 24, "a table entry is 24 bytes");
+  static_assert(UGO_FEC_KERNEL_ACK == ugo::kern::kKAck, "kernel class matches ack_kernels.hpp");
+  if (out) *out = nullptr;
+  if (!c || !out || !ugo::ackargs::window_ok(window_packets)) return UGO_FEC_ERR_INVALID_ARG;
+  if (c->poisoned) return UGO_FEC_ERR_HIP;
+  DeviceGuard g(c->device);
+  if (!g.ok) return UGO_FEC_ERR_NO_DEVICE;
+  ugo_ack_rx* rx = new (std::nothrow) ugo_ack_rx();
+  if (!rx) return UGO_FEC_ERR_HIP;
+  rx->ctx = c;
+  rx->m.ctx = c;
+  rx->m.window_packets = window_packets;
+  const size_t bitmap_bytes = window_packets / 8;
+  if (hipMalloc(&rx->m.bits, bitmap_bytes) != hipSuccess || hipMalloc(&rx->m.rec, sizeof(ugo_ack_state)) != hipSuccess ||
+      hipMemset(rx->m.bits, 0, bitmap_bytes) != hipSuccess ||
+      hipMemset(rx->m.rec, 0, sizeof(ugo_ack_state)) != hipSuccess ||
+      hipStreamSynchronize(nullptr) != hipSuccess) {  // the fills ran on the null stream
+    (void)hipGetLastError();
+    ugo_fec_ack_rx_destroy(rx);
+    return UGO_FEC_ERR_HIP;
+  }
+  *out = rx;
+  return UGO_FEC_OK;
+}
+
+void ugo_fec_ack_rx_destroy(ugo_ack_rx* rx) {
+  if (!rx) return;
+  {
+    DeviceGuard g(rx->ctx->device);
+    for (ugo_ack_rx_set* set : rx->sets)
+      if (set->used) (void)hipStreamSynchronize(set->last);
+    (void)hipFree(rx->m.bits);
+    (void)hipFree(rx->m.rec);
+  }
+  delete rx;
+}
+
+int ugo_fec_ack_rx_state(ugo_ack_rx* rx, ugo_ack_state* host_out) {
+  if (!rx || !host_out) return UGO_FEC_ERR_INVALID_ARG;
+  DeviceGuard g(rx->ctx->device);
+  if (!g.ok) return UGO_FEC_ERR_NO_DEVICE;
+  for (ugo_ack_rx_set* set : rx->sets)
+    if (set->used && hipStreamSynchronize(set->last) != hipSuccess) return UGO_FEC_ERR_HIP;
+  return hip_status(hipMemcpy(host_out, rx->m.rec, sizeof(*host_out), hipMemcpyDeviceToHost));
+}
+
+int ugo_fec_ack_rx_bitmap(ugo_ack_rx* rx, uint64_t** bitmap_dev, size_t* window_packets) {
+  if (!rx || !bitmap_dev || !window_packets) return UGO_FEC_ERR_INVALID_ARG;
+  *bitmap_dev = rx->m.bits;
+  *window_packets = rx->m.window_packets;
+  return UGO_FEC_OK;
+}
+
+namespace {
+// The body of ugo_fec_ack_set_create; its host containers may throw std::bad_alloc.
+int ack_set_build(ugo_fec* c, ugo_ack_rx* const* rxs, size_t nconn, ugo_ack_rx_set** out) {
+  std::vector<const ugo::ackargs::Member*> ms(nconn);
+  for (size_t i = 0; i < nconn; ++i) ms[i] = rxs[i] ? &rxs[i]->m : nullptr;
+  if (!ugo::ackargs::members_ok(c, ms.data(), nconn)) return UGO_FEC_ERR_INVALID_ARG;
+  if (c->poisoned) return UGO_FEC_ERR_HIP;
+  const std::vector<ugo::kern::AckEntry> host = ugo::ackargs::build_table(ms.data(), nconn);
+  DeviceGuard g(c->device);
+  if (!g.ok) return UGO_FEC_ERR_NO_DEVICE;
+  ugo_ack_rx_set* set = new (std::nothrow) ugo_ack_rx_set();
+  if (!set) return UGO_FEC_ERR_HIP;
+  set->ctx = c;
+  const size_t nwords = ugo::kern::kAckScanBlock + 1;
+  if (hipMalloc(&set->table, nconn * sizeof(host[0])) != hipSuccess ||
+      hipMalloc(&set->gathered, nconn * sizeof(ugo_ack_state)) != hipSuccess ||
+      hipMalloc(&set->call, nconn * sizeof(ugo::kern::AckCall)) != hipSuccess ||
+      hipMalloc(&set->slot_local, nconn * sizeof(uint32_t)) != hipSuccess ||
+      hipMalloc(&set->words, nwords * sizeof(uint64_t)) != hipSuccess ||
+      hipMemset(set->call, 0, nconn * sizeof(ugo::kern::AckCall)) != hipSuccess ||
+      hipMemset(set->slot_local, 0, nconn * sizeof(uint32_t)) != hipSuccess ||
+      hipMemset(set->words, 0, nwords * sizeof(uint64_t)) != hipSuccess ||
+      hipMemcpy(set->table, host.data(), nconn * sizeof(host[0]), hipMemcpyHostToDevice) != hipSuccess ||
+      hipStreamSynchronize(nullptr) != hipSuccess) {
+    (void)hipGetLastError();
+    ugo_fec_ack_set_destroy(set);
+    return UGO_FEC_ERR_HIP;
+  }
+  try {
+    set->members.assign(rxs, rxs + nconn);
+    for (ugo_ack_rx* rx : set->members) rx->sets.push_back(set);
+  } catch (const std::bad_alloc&) {
+    ugo_fec_ack_set_destroy(set);  // takes the set out of the members that had it already
+    throw;
+  }
+  *out = set;
+  return UGO_FEC_OK;
+}
+}  // namespace
+
+int ugo_fec_ack_set_create(ugo_fec* c, ugo_ack_rx* const* rxs, size_t nconn, ugo_ack_rx_set** out) {
+  if (out) *out = nullptr;
+  if (!c || !rxs || !out || nconn == 0 || nconn > ugo::kern::kAckSetMaxConn) return UGO_FEC_ERR_INVALID_ARG;
+  try {
+    return ack_set_build(c, rxs, nconn, out);
+  } catch (const std::bad_alloc&) {  // nothing throws through the C boundary
+    return UGO_FEC_ERR_HIP;
+  }
+}
+
+void ugo_fec_ack_set_destroy(ugo_ack_rx_set* set) {
+  if (!set) return;
+  {
+    DeviceGuard g(set->ctx->device);
+    if (set->used) (void)hipStreamSynchronize(set->last);
+    (void)hipFree(set->table);
+    (void)hipFree(set->gathered);
+    (void)hipFree(set->call);
+    (void)hipFree(set->slot_local);
+    (void)hipFree(set->words);
+  }
+  for (ugo_ack_rx* rx : set->members)
+    rx->sets.erase(std::remove(rx->sets.begin(), rx->sets.end(), set), rx->sets.end());
+  delete set;
+}
+
+int ugo_fec_ack_set_receive(ugo_ack_rx_set* set, const ugo_pkt_info* info, const uint32_t* conn_of, size_t npk,
+                            const uint8_t* seg_status, size_t max_segments, uint64_t now_us, void* stream) {
+  if (const int st = ack_enter(set)) return st;
+  if (npk == 0) return UGO_FEC_OK;
+  if (!ugo::ackargs::receive_ok(info, conn_of, npk, seg_status, max_segments)) return UGO_FEC_ERR_INVALID_ARG;
+  ugo_fec* c = set->ctx;
+  DeviceGuard g(c->device);
+  if (!g.ok) return UGO_FEC_ERR_NO_DEVICE;
+  if (!device_view(info) || !device_view(conn_of) || !device_view(seg_status)) return UGO_FEC_ERR_INVALID_ARG;
+  TimerScope ts(c);
+  ugo::kern::AckReceiveArgs a{};
+  a.table = set->table;
+  a.call = set->call;
+  a.info = info;
+  a.conn_of = conn_of;
+  a.seg_status = seg_status;
+  a.npk = npk;
+  a.now_us = now_us;
+  a.nconn = static_cast<uint32_t>(set->members.size());
+  a.max_segments = static_cast<uint32_t>(max_segments);
+  set->last = static_cast<hipStream_t>(stream);
+  set->used = true;
+  return hip_status(ugo::kern::launch_ack_receive(a, set->last));
+}
+
+int ugo_fec_ack_set_touch(ugo_ack_rx_set* set, const uint8_t* flags, void* stream) {
+  if (const int st = ack_enter(set)) return st;
+  if (!flags) return UGO_FEC_ERR_INVALID_ARG;
+  ugo_fec* c = set->ctx;
+  DeviceGuard g(c->device);
+  if (!g.ok) return UGO_FEC_ERR_NO_DEVICE;
+  if (!device_view(flags)) return UGO_FEC_ERR_INVALID_ARG;
+  TimerScope ts(c);
+  set->last = static_cast<hipStream_t>(stream);
+  set->used = true;
+  return hip_status(
+      ugo::kern::launch_ack_touch(set->table, static_cast<uint32_t>(set->members.size()), flags, set->last));
+}
+
+int ugo_fec_ack_set_attach(ugo_ack_rx_set* set, uint64_t now_us, const uint64_t* first_packet,
+                           const uint32_t* n_packets, const uint64_t* total, const uint8_t* may_ack_only,
+                           size_t max_packets, ugo_pkt_info* info, uint64_t* ranges, size_t max_ranges,
+                           uint32_t* conn_of, uint64_t* total_out, uint8_t* attached, void* stream) {
+  if (const int st = ack_enter(set)) return st;
+  if (!ugo::ackargs::attach_ok(first_packet, n_packets, total, max_packets, info, ranges, max_ranges, conn_of,
+                               total_out, attached))
+    return UGO_FEC_ERR_INVALID_ARG;
+  ugo_fec* c = set->ctx;
+  DeviceGuard g(c->device);
+  if (!g.ok) return UGO_FEC_ERR_NO_DEVICE;
+  if (!device_view(first_packet) || !device_view(n_packets) || !device_view(total) || !device_view(may_ack_only) ||
+      !device_view(info) || !device_view(ranges) || !device_view(conn_of) || !device_view(total_out) ||
+      !device_view(attached))
+    return UGO_FEC_ERR_INVALID_ARG;
+  TimerScope ts(c);
+  ugo::kern::AckAttachArgs a{};
+  a.table = set->table;
+  a.first_packet = reinterpret_cast<const unsigned long long*>(first_packet);
+  a.n_packets = n_packets;
+  a.total = reinterpret_cast<const unsigned long long*>(total);
+  a.may_ack_only = may_ack_only;
+  a.info = info;
+  a.ranges = ranges;
+  a.conn_of = conn_of;
+  a.total_out = reinterpret_cast<unsigned long long*>(total_out);
+  a.attached = attached;
+  a.slot_local = set->slot_local;
+  a.block_slots = set->words;
+  a.total_in = set->words + ugo::kern::kAckScanBlock;
+  a.now_us = now_us;
+  a.max_packets = max_packets;
+  a.nconn = static_cast<uint32_t>(set->members.size());
+  a.max_ranges = static_cast<uint32_t>(max_ranges);
+  set->last = static_cast<hipStream_t>(stream);
+  set->used = true;
+  return hip_status(ugo::kern::launch_ack_attach(a, set->last));
+}
+
+int ugo_fec_ack_set_state(ugo_ack_rx_set* set, ugo_ack_state* host_out) {
+  if (!set || !host_out) return UGO_FEC_ERR_INVALID_ARG;
+  DeviceGuard g(set->ctx->device);
+  if (!g.ok) return UGO_FEC_ERR_NO_DEVICE;
+  const uint32_t nconn = static_cast<uint32_t>(set->members.size());
+  if (ugo::kern::launch_ack_gather(set->table, nconn, set->gathered, set->last) != hipSuccess ||
       hipStreamSynchronize(set->last) != hipSuccess)
     return UGO_FEC_ERR_HIP;
   return hip_status(hipMemcpy(host_out, set->gathered, nconn * sizeof(*host_out), hipMemcpyDeviceToHost));

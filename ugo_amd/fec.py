@@ -42,6 +42,7 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ugo_fec.h")
 CONN_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ugo_fec_conn.h")
 PKT_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ugo_pkt.h")
 STREAM_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ugo_stream.h")
+ACK_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ugo_ack.h")
 
 OK = 0
 RECONSTRUCT_DATA_ONLY = 1
@@ -105,7 +106,8 @@ PKT_INFO_DTYPE = np.dtype([("packet_number", "<u8"), ("stop_waiting", "<u8"), ("
                            ("fec_flag_lo", "u1"), ("reserved", "u1", (10,))])
 # include/ugo_fec.h launch timing
 KERNEL_NAMES = {1: "encode", 2: "reconstruct", 3: "prepare", 4: "bytes", 5: "rx_assemble", 6: "tx_assemble",
-                7: "packet_decode", 8: "packet_encode", 9: "stream_deliver", 10: "stream_read", 11: "stream_tx"}
+                7: "packet_decode", 8: "packet_encode", 9: "stream_deliver", 10: "stream_read", 11: "stream_tx",
+                12: "ack"}
 KERNEL_IDS = {v: k for k, v in KERNEL_NAMES.items()}
 LAUNCH_TIME_DTYPE = np.dtype([("kernel", "<u4"), ("ms", "<f4")])
 PKT_SEGMENT_DTYPE = np.dtype([("offset", "<u8"), ("data_off", "<u4"), ("len", "<u2"), ("avail", "<u2")])
@@ -140,6 +142,16 @@ STREAM_TX_STATE_DTYPE = np.dtype([("base", "<u8"), ("write_pos", "<u8"), ("tail"
                                   ("bytes_new", "<u8"), ("bytes_retransmitted", "<u8"), ("rq_rejected", "<u8"),
                                   ("rq_len", "<u4"), ("rq_head", "<u4")])
 assert STREAM_TX_STATE_DTYPE.itemsize == 80 and STREAM_TX_RQ_DTYPE.itemsize == 16
+# include/ugo_ack.h, receive histories
+ACK_MIN_WINDOW = 1024
+ACK_MAX_WINDOW = 1 << 20
+ACK_MAX_OUTSTANDING = 1000
+ACK_TOO_MANY_OUTSTANDING = 1  # ugo_ack_state.err
+ACK_NOT_ATTACHED, ACK_ATTACHED, ACK_TRUNCATED = 0, 1, 2  # attach's attached[c]
+ACK_STATE_DTYPE = np.dtype([("largest_in_order", "<u8"), ("largest_observed", "<u8"), ("ignore_below", "<u8"),
+                            ("lo_time_us", "<u8"), ("fresh", "<u8"), ("old", "<u8"), ("out_of_window", "<u8"),
+                            ("outstanding", "<u4"), ("changed", "u1"), ("err", "u1"), ("reserved", "u1", (2,))])
+assert ACK_STATE_DTYPE.itemsize == 64
 
 
 def load_library(path: str = LIB_PATH):
@@ -207,6 +219,18 @@ def load_library(path: str = LIB_PATH):
     lib.ugo_fec_stream_tx_set_plan.argtypes = [vp, vp, sz, sz, sz, vp, vp, vp, vp, vp, vp, vp]
     lib.ugo_fec_stream_tx_set_encode.argtypes = [vp, vp, vp, sz, vp, sz, vp, sz, vp, u, vp, sz, vp, vp, vp]
     lib.ugo_fec_stream_tx_set_state.argtypes = [vp, vp]
+    lib.ugo_fec_ack_rx_create.argtypes = [vp, sz, ctypes.POINTER(vp)]
+    lib.ugo_fec_ack_rx_destroy.argtypes = [vp]
+    lib.ugo_fec_ack_rx_destroy.restype = None
+    lib.ugo_fec_ack_rx_state.argtypes = [vp, vp]
+    lib.ugo_fec_ack_rx_bitmap.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(sz)]
+    lib.ugo_fec_ack_set_create.argtypes = [vp, vp, sz, ctypes.POINTER(vp)]
+    lib.ugo_fec_ack_set_destroy.argtypes = [vp]
+    lib.ugo_fec_ack_set_destroy.restype = None
+    lib.ugo_fec_ack_set_receive.argtypes = [vp, vp, vp, sz, vp, sz, u64, vp]
+    lib.ugo_fec_ack_set_touch.argtypes = [vp, vp, vp]
+    lib.ugo_fec_ack_set_attach.argtypes = [vp, u64, vp, vp, vp, vp, sz, vp, vp, sz, vp, vp, vp, vp]
+    lib.ugo_fec_ack_set_state.argtypes = [vp, vp]
     lib.ugo_fec_reconstruct_rows.argtypes = [vp, vp, vp, sz, sz, vp, sz, sz, u, vp, vp]
     lib.ugo_fec_lossy_groups.argtypes = [vp, vp, sz, u, vp, vp, vp]
     lib.ugo_fec_rx_recover_host.argtypes = [vp, vp, sz, vp, sz, vp, ctypes.c_uint64, sz, sz, vp, vp, vp, sz, sz, vp,
@@ -223,8 +247,9 @@ def load_library(path: str = LIB_PATH):
     return lib
 
 
-def header_symbols(paths=(HEADER_PATH, CONN_HEADER_PATH, PKT_HEADER_PATH, STREAM_HEADER_PATH)) -> List[str]:
-    """Every entry point declared in include/ugo_fec.h, ugo_fec_conn.h, ugo_pkt.h and ugo_stream.h."""
+def header_symbols(paths=(HEADER_PATH, CONN_HEADER_PATH, PKT_HEADER_PATH, STREAM_HEADER_PATH,
+                          ACK_HEADER_PATH)) -> List[str]:
+    """Every entry point declared in include/ugo_fec.h, ugo_fec_conn.h, ugo_pkt.h, ugo_stream.h and ugo_ack.h."""
     out = set()
     for path in paths:
         src = open(path).read()
@@ -1155,6 +1180,158 @@ class StreamTxSet:
         """The members' records (STREAM_TX_STATE_DTYPE [nconn]); waits for the last call on the set."""
         out = np.zeros(self.nconn, STREAM_TX_STATE_DTYPE)
         _raise(load_library().ugo_fec_stream_tx_set_state(self._h, out.ctypes.data))
+        return out
+
+
+class AckRx:
+    """A connection's receive history on the GPU (include/ugo_ack.h): the
+    packetReceiver's state, a ring bitmap of window_packets numbers and a
+    record.  Every call goes through an AckRxSet; a set of one is the
+    single-connection form."""
+
+    def __init__(self, enc: Encoder, window_packets: int = 4096):
+        self.check_window(window_packets)
+        h = ctypes.c_void_p()
+        _raise(load_library().ugo_fec_ack_rx_create(enc._h, window_packets, ctypes.byref(h)))
+        self._h, self._enc = h, enc  # the context must outlive the history
+        self.window_packets = window_packets
+        self.device = enc.device
+
+    @staticmethod
+    def check_window(window_packets: int):
+        _require(ACK_MIN_WINDOW <= window_packets <= ACK_MAX_WINDOW and window_packets & (window_packets - 1) == 0,
+                 f"window_packets must be a power of two in [{ACK_MIN_WINDOW}, 2^20]")
+
+    def close(self):
+        if getattr(self, "_h", None):
+            load_library().ugo_fec_ack_rx_destroy(self._h)
+            self._h = None
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def state(self) -> np.ndarray:
+        """The record (ACK_STATE_DTYPE scalar); waits for the last call of the sets it is in."""
+        out = np.zeros(1, ACK_STATE_DTYPE)
+        _raise(load_library().ugo_fec_ack_rx_state(self._h, out.ctypes.data))
+        return out[0]
+
+    def bitmap(self):
+        """The ring bitmap as an int64 CUDA tensor [window_packets / 64] over the
+        device memory itself (packet number n is bit n & 63 of word
+        (n & (window_packets - 1)) >> 6); valid while this object lives."""
+        p, n = ctypes.c_void_p(), ctypes.c_size_t()
+        _raise(load_library().ugo_fec_ack_rx_bitmap(self._h, ctypes.byref(p), ctypes.byref(n)))
+        t = torch.as_tensor(_DeviceBytes(p.value, n.value // 8, self), device=torch.device("cuda", self.device))
+        return t.view(torch.int64)
+
+
+class AckRxSet:
+    """An ordered set of receive histories (ugo_fec_ack_set_*): receive for a
+    decoded batch that holds the packets of many connections, attach to write
+    every member's SACK into the arrays StreamTxSet.plan left for
+    StreamTxSet.encode.  Operands are tensors in device or pinned host memory.
+    Nothing is synchronised but states().  The set does not own its members;
+    close it before them."""
+
+    def __init__(self, enc: Encoder, rxs):
+        rxs = list(rxs)
+        self.check_members(enc, rxs)
+        arr = (ctypes.c_void_p * len(rxs))(*[rx._h.value for rx in rxs])
+        h = ctypes.c_void_p()
+        _raise(load_library().ugo_fec_ack_set_create(enc._h, ctypes.addressof(arr), len(rxs), ctypes.byref(h)))
+        self._h, self._enc, self.rxs = h, enc, rxs  # context and members must outlive the set
+        self.nconn = len(rxs)
+        self.device = enc.device
+
+    @staticmethod
+    def check_members(enc, rxs):
+        _require(0 < len(rxs) <= STREAM_SET_MAX_CONN, f"a set holds 1 to {STREAM_SET_MAX_CONN} histories")
+        _require(all(isinstance(rx, AckRx) and getattr(rx, "_h", None) for rx in rxs), "members must be open AckRx")
+        _require(all(rx._enc is enc for rx in rxs), "every member must belong to the set's context")
+        _require(len({id(rx) for rx in rxs}) == len(rxs), "a history may be listed once")
+
+    def check_per_conn(self, t, element_size: int, name: str):
+        _require(t.is_contiguous() and t.element_size() == element_size and t.numel() == self.nconn and
+                 not t.dtype.is_floating_point, f"{name} must be nconn contiguous {8 * element_size}-bit integers")
+
+    def close(self):
+        if getattr(self, "_h", None):
+            load_library().ugo_fec_ack_set_destroy(self._h)
+            self._h = None
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def receive(self, info, conn_of, now_us: int, seg_status=None, npackets: Optional[int] = None, stream=None):
+        """ugo_fec_ack_set_receive: info uint8 [>= npackets, 64] as packet_decode
+        returned it, conn_of int32 [>= npackets] the member of each packet,
+        seg_status uint8 [>= npackets, max_segments] as StreamRxSet.deliver
+        returned it, or None.  npackets defaults to info.shape[0]."""
+        npk = info.shape[0] if npackets is None else npackets
+        _require(0 <= npk <= info.shape[0] and 0 <= now_us < 1 << 64)
+        _require(info.is_contiguous() and info.element_size() == 1 and info.dim() == 2 and info.shape[1] == 64)
+        _require(conn_of.is_contiguous() and conn_of.element_size() == 4 and conn_of.numel() >= npk and
+                 not conn_of.dtype.is_floating_point, "conn_of must be npackets contiguous 32-bit integers")
+        max_segments = 0
+        if seg_status is not None:
+            _require(seg_status.is_contiguous() and seg_status.element_size() == 1 and seg_status.dim() == 2 and
+                     seg_status.shape[0] >= npk and 1 <= seg_status.shape[1] <= 0xffff)
+            max_segments = seg_status.shape[1]
+        _raise(load_library().ugo_fec_ack_set_receive(
+            self._h, info.data_ptr(), conn_of.data_ptr(), npk, None if seg_status is None else seg_status.data_ptr(),
+            max_segments, now_us, _stream_handle(stream)))
+
+    def touch(self, flags, stream=None):
+        """changed = 1 for the members with flags[c] != 0 (uint8 [nconn])."""
+        self.check_per_conn(flags, 1, "flags")
+        _raise(load_library().ugo_fec_ack_set_touch(self._h, flags.data_ptr(), _stream_handle(stream)))
+
+    def attach(self, now_us: int, first_packet, n_packets, total, info, ranges, conn_of, may_ack_only=None,
+               total_out=None, attached=None, stream=None):
+        """ugo_fec_ack_set_attach: first_packet int64 [nconn], n_packets int32
+        [nconn] and total int64 [1] as StreamTxSet.plan returned them; info uint8
+        [max_packets, 64], ranges int64 [max_packets, max_ranges, 2] and conn_of
+        int32 [max_packets] the arrays StreamTxSet.encode will be given;
+        may_ack_only uint8 [nconn] or None.  Returns (total_out int64 [1],
+        attached uint8 [nconn] of ACK_*); both may be given, and total_out may
+        be total itself."""
+        max_packets = info.shape[0]
+        _require(0 <= now_us < 1 << 64 and max_packets <= 1 << 31)
+        _require(info.is_contiguous() and info.element_size() == 1 and info.dim() == 2 and info.shape[1] == 64)
+        _require(ranges.is_contiguous() and ranges.element_size() == 8 and ranges.dim() == 3 and
+                 ranges.shape[0] == max_packets and ranges.shape[1] <= 0xffff and ranges.shape[2] == 2)
+        _require(conn_of.is_contiguous() and conn_of.element_size() == 4 and conn_of.numel() == max_packets and
+                 not conn_of.dtype.is_floating_point)
+        self.check_per_conn(first_packet, 8, "first_packet")
+        self.check_per_conn(n_packets, 4, "n_packets")
+        _require(total.numel() == 1 and total.element_size() == 8)
+        if may_ack_only is not None:
+            self.check_per_conn(may_ack_only, 1, "may_ack_only")
+        dev = torch.device("cuda", self.device)
+        if total_out is None:
+            total_out = torch.zeros(1, dtype=torch.int64, device=dev)
+        if attached is None:
+            attached = torch.zeros(self.nconn, dtype=torch.uint8, device=dev)
+        _require(total_out.numel() == 1 and total_out.element_size() == 8)
+        self.check_per_conn(attached, 1, "attached")
+        _raise(load_library().ugo_fec_ack_set_attach(
+            self._h, now_us, first_packet.data_ptr(), n_packets.data_ptr(), total.data_ptr(),
+            None if may_ack_only is None else may_ack_only.data_ptr(), max_packets, info.data_ptr(),
+            ranges.data_ptr() if ranges.numel() else None, ranges.shape[1], conn_of.data_ptr(), total_out.data_ptr(),
+            attached.data_ptr(), _stream_handle(stream)))
+        return total_out, attached
+
+    def states(self) -> np.ndarray:
+        """The members' records (ACK_STATE_DTYPE [nconn]); waits for the last call on the set."""
+        out = np.zeros(self.nconn, ACK_STATE_DTYPE)
+        _raise(load_library().ugo_fec_ack_set_state(self._h, out.ctypes.data))
         return out
 
 

@@ -68,7 +68,8 @@ extern "C" {
  *    UGO_FEC_KERNEL_STREAM_READ; the send windows, ugo_fec_stream_tx_*
  *    (ugo_stream.h), with UGO_PKT_OUT_OF_WINDOW and UGO_FEC_KERNEL_STREAM_TX;
  *    the receive histories, ugo_fec_ack_* (ugo_ack.h), with UGO_FEC_KERNEL_ACK
- *    (12, defined there). */
+ *    (12, defined there); the sent histories, ugo_fec_sent_* (ugo_sent.h), with
+ *    UGO_FEC_KERNEL_SENT (13, defined there). */
 #define UGO_FEC_ABI_VERSION 9
 
 /* Status codes.  1..5 map 1:1 onto the klauspost/reedsolomon error values

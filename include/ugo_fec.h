@@ -69,7 +69,8 @@ extern "C" {
  *    (ugo_stream.h), with UGO_PKT_OUT_OF_WINDOW and UGO_FEC_KERNEL_STREAM_TX;
  *    the receive histories, ugo_fec_ack_* (ugo_ack.h), with UGO_FEC_KERNEL_ACK
  *    (12, defined there); the sent histories, ugo_fec_sent_* (ugo_sent.h), with
- *    UGO_FEC_KERNEL_SENT (13, defined there). */
+ *    UGO_FEC_KERNEL_SENT (13, defined there); congestion control,
+ *    ugo_fec_cc_* (ugo_cc.h), with UGO_FEC_KERNEL_CC (14, defined there). */
 #define UGO_FEC_ABI_VERSION 9
 
 /* Status codes.  1..5 map 1:1 onto the klauspost/reedsolomon error values

@@ -26,6 +26,10 @@
 //                              scan inside it, and acked / nacks for every
 //                              slot: free, count missing, queue
 //           k_sent_ack_finish  per member: the record, the event row
+//         ugo_fec_cc_sent_ack (include/ugo_cc.h) is the same five, apply and
+//         finish in a second instantiation that also gathers the member's
+//         ugo_cc_row: the highest number lost, the highest freed, and the
+//         freed at or below split[c].
 //         The time is (ACKs + their rows) + (the members' outstanding spans),
 //         never their product, and a member with a long span gets one block
 //         per 1,024 numbers of it.  An accepted ACK that acknowledges from the
@@ -62,7 +66,8 @@ constexpr uint32_t kChThreads = 256; // threads of a chunk's block: kSentChunk /
 constexpr uint32_t kChRounds = kSentChunk / kChThreads;
 
 static_assert(sizeof(SentSlot) == 32 && sizeof(SentRecord) == 160 && sizeof(ugo_sent_event) == 64 &&
-                  sizeof(SentCall) == 128 && sizeof(SentEntry) == 56 && sizeof(ugo_stream_tx_rq_entry) == 16,
+                  sizeof(SentCall) == 128 && sizeof(SentEntry) == 56 && sizeof(ugo_stream_tx_rq_entry) == 16 &&
+                  sizeof(SentCcCall) == 32 && sizeof(ugo_cc_row) == 32,
               "layouts");
 
 // ---------------------------------------------------------------- wave helpers (wave64)
@@ -557,9 +562,18 @@ struct ChunkAcc {  // a block's sums before they leave it
   uint32_t acked_pk, lost_pk, lost_segs, qfreed, qfreed_segs, flags;
 };
 
+struct CcAcc {  // the same, for what ugo_fec_cc_sent_ack adds (include/ugo_cc.h)
+  u64 max_lost, max_acked;
+  uint32_t acked_le;
+};
+
+// kCc: the body of ugo_fec_cc_sent_ack, which also gathers the member's
+// ugo_cc_row; the plain instantiation is the kernel ugo_fec_sent_set_ack had.
+template <bool kCc>
 __global__ __launch_bounds__(kChThreads) void k_sent_ack_apply(SentAckArgs a) {
   __shared__ int2 lds[kChThreads / 64];
   __shared__ ChunkAcc acc;
+  __shared__ CcAcc cacc;
   const uint32_t b = blockIdx.x, c = a.chunk_member[b];
   SentCall* k = a.call + c;
   const uint32_t n_acc = k->n_acc;
@@ -569,6 +583,12 @@ __global__ __launch_bounds__(kChThreads) void k_sent_ack_apply(SentAckArgs a) {
   u64 first, last;
   if (!chunk_geo(e, *rec, b, true, first, last)) return;
   if (threadIdx.x == 0) acc = ChunkAcc{};
+  u64 split = 0;
+  CcAcc ct{};
+  if constexpr (kCc) {
+    if (threadIdx.x == 0) cacc = CcAcc{};
+    split = a.split[c];
+  }
   const u64 lam = k->max_n, lio0 = rec->lio;
   // the sums of the member's chunks before this one
   int cd = 0, ce = 0;
@@ -614,6 +634,10 @@ __global__ __launch_bounds__(kChThreads) void k_sent_ack_apply(SentAckArgs a) {
             e.slots[pos] = SentSlot{};
             t.acked_pk++;
             t.acked_bytes += s.len;
+            if constexpr (kCc) {
+              if (n > ct.max_acked) ct.max_acked = n;
+              ct.acked_le += n <= split;
+            }
             if (s.state == UGO_SENT_IN_FLIGHT) {
               t.bytes += s.len;
             } else {
@@ -631,6 +655,9 @@ __global__ __launch_bounds__(kChThreads) void k_sent_ack_apply(SentAckArgs a) {
               t.lost_pk++;
               t.lost_bytes += s.len;
               t.lost_segs += s.n_segments;
+              if constexpr (kCc) {
+                if (n > ct.max_lost) ct.max_lost = n;
+              }
             }
             if (m8 != s.missing || lose) {
               s.missing = m8;
@@ -673,7 +700,25 @@ __global__ __launch_bounds__(kChThreads) void k_sent_ack_apply(SentAckArgs a) {
     if (t.qfreed_segs) atomicAdd(&acc.qfreed_segs, t.qfreed_segs);
     if (t.flags) atomicOr(&acc.flags, t.flags);
   }
+  if constexpr (kCc) {
+    ct.max_lost = wave_max(ct.max_lost);
+    ct.max_acked = wave_max(ct.max_acked);
+    ct.acked_le = wave_sum(ct.acked_le);
+    if (lane_id() == 0) {
+      if (ct.max_lost) atomicMax(&cacc.max_lost, ct.max_lost);
+      if (ct.max_acked) atomicMax(&cacc.max_acked, ct.max_acked);
+      if (ct.acked_le) atomicAdd(&cacc.acked_le, ct.acked_le);
+    }
+  }
   __syncthreads();
+  if constexpr (kCc) {
+    if (threadIdx.x == 0) {
+      SentCcCall* kc = a.cc_call + c;
+      if (cacc.max_lost) atomicMax(&kc->max_lost, cacc.max_lost);
+      if (cacc.max_acked) atomicMax(&kc->max_acked, cacc.max_acked);
+      if (cacc.acked_le) atomicAdd(&kc->acked_le, cacc.acked_le);
+    }
+  }
   if (threadIdx.x == 0) {
     if (acc.bytes) atomicAdd(&k->bytes, acc.bytes);
     if (acc.acked_bytes) atomicAdd(&k->acked_bytes, acc.acked_bytes);
@@ -689,12 +734,24 @@ __global__ __launch_bounds__(kChThreads) void k_sent_ack_apply(SentAckArgs a) {
   }
 }
 
+template <bool kCc>
 __global__ __launch_bounds__(256) void k_sent_ack_finish(SentAckArgs a) {
   const uint32_t c = blockIdx.x * 256u + threadIdx.x;
   if (c >= a.nconn) return;
   const SentCall k = a.call[c];
   SentRecord* rec = a.table[c].rec;
   ugo_sent_event ev{};
+  if constexpr (kCc) {  // the member's row, whole; all zero with no accepted ACK
+    ugo_cc_row row{};
+    if (k.n_acc) {
+      const SentCcCall kc = a.cc_call[c];
+      row.max_lost = kc.max_lost;
+      row.max_acked = kc.max_acked;
+      row.acked_le = kc.acked_le;
+      if (kc.max_lost | kc.max_acked) a.cc_call[c] = SentCcCall{};
+    }
+    a.rows[c] = row;
+  }
   if (k.unsent) rec->unsent_acks += k.unsent;
   if (k.w_max > rec->largest_with_ack) rec->largest_with_ack = k.w_max;
   if (k.n_acc) {
@@ -994,14 +1051,17 @@ hipError_t launch_sent_record(const SentRecordArgs& a, hipStream_t s) {
 }
 
 hipError_t launch_sent_ack(const SentAckArgs& a, hipStream_t s) {
+  const bool cc = a.rows != nullptr;
+  const uint32_t kid = cc ? kKCc : kKSent;
   if (a.npk != 0) {
     const dim3 per_packet(static_cast<uint32_t>((a.npk + kPkBlock - 1u) / kPkBlock));
-    launch(kKSent, k_sent_ack_scan, per_packet, dim3(kPkBlock), 0, s, a);
-    launch(kKSent, k_sent_ack_marks, per_packet, dim3(kPkBlock), 0, s, a);
-    launch(kKSent, k_sent_ack_sum, dim3(a.nchunks), dim3(kChThreads), 0, s, a);
-    launch(kKSent, k_sent_ack_apply, dim3(a.nchunks), dim3(kChThreads), 0, s, a);
+    launch(kid, k_sent_ack_scan, per_packet, dim3(kPkBlock), 0, s, a);
+    launch(kid, k_sent_ack_marks, per_packet, dim3(kPkBlock), 0, s, a);
+    launch(kid, k_sent_ack_sum, dim3(a.nchunks), dim3(kChThreads), 0, s, a);
+    launch(kid, cc ? k_sent_ack_apply<true> : k_sent_ack_apply<false>, dim3(a.nchunks), dim3(kChThreads), 0, s, a);
   }
-  launch(kKSent, k_sent_ack_finish, dim3((a.nconn + 255u) / 256u), dim3(256), 0, s, a);
+  launch(kid, cc ? k_sent_ack_finish<true> : k_sent_ack_finish<false>, dim3((a.nconn + 255u) / 256u), dim3(256), 0, s,
+         a);
   return hipGetLastError();
 }
 

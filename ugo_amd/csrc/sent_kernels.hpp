@@ -6,6 +6,7 @@
 
 #include <cstdint>
 
+#include "../../include/ugo_cc.h"
 #include "../../include/ugo_sent.h"
 
 namespace ugo {
@@ -19,6 +20,7 @@ constexpr uint32_t kSentSetMaxConn = 1u << 20;
 constexpr uint32_t kSentChunk = 1024;      // numbers per block of the per-member scans (= UGO_SENT_MIN_WINDOW)
 constexpr uint32_t kSentScanBlock = 1024;  // members per block of drain's scan over the members
 constexpr uint32_t kKSent = 13;            // UGO_FEC_KERNEL_SENT
+constexpr uint32_t kKCc = 14;              // UGO_FEC_KERNEL_CC
 
 // One member of a set, uploaded once by ugo_fec_sent_set_create (56 bytes).
 struct SentEntry {
@@ -53,6 +55,15 @@ struct SentCall {
 };
 constexpr uint32_t kCallErr = 1, kCallRtt = 2, kCallTouch = 4, kCallStop = 8;
 
+// What ugo_fec_cc_sent_ack gathers beside SentCall (device, owned by the set,
+// all zero between calls; the plain set_ack never touches it).  32 bytes.
+struct SentCcCall {
+  unsigned long long max_lost;   // the highest number the call declared lost
+  unsigned long long max_acked;  // the highest number whose slot the call freed
+  uint32_t acked_le;             // freed slots with n <= split[c]
+  uint32_t reserved[3];
+};
+
 struct SentRecordArgs {
   const SentEntry* table;
   SentCall* call;  // [nconn]
@@ -77,12 +88,17 @@ struct SentAckArgs {
   const uint64_t* ranges;
   const uint32_t* conn_of;
   ugo_sent_event* events;          // [nconn]
+  // ugo_fec_cc_sent_ack only (include/ugo_cc.h); null in ugo_fec_sent_set_ack
+  SentCcCall* cc_call;             // [nconn]
+  const unsigned long long* split; // [nconn]
+  ugo_cc_row* rows;                // [nconn]
   uint64_t npk;
   uint64_t now_us;
   uint32_t nconn;
   uint32_t max_ranges;
   uint32_t nchunks;
 };
+// rows != nullptr: the cc form, whose launches report as UGO_FEC_KERNEL_CC.
 hipError_t launch_sent_ack(const SentAckArgs& a, hipStream_t s);
 
 struct SentRtoArgs {

@@ -35,7 +35,9 @@
 #include "stream_tx_kernels.hpp"
 #include "ack_kernels.hpp"
 #include "host/ack_args.hpp"
+#include "host/cc_args.hpp"
 #include "host/sent_args.hpp"
+#include "cc_kernels.hpp"
 #include "sent_kernels.hpp"
 
 namespace {
@@ -3081,6 +3083,8 @@ struct ugo_sent_tx_set {
   ugo::kern::SentEntry* table = nullptr;  // device, [nconn], uploaded once
   ugo_sent_state* gathered = nullptr;     // device, [nconn], for ugo_fec_sent_set_state
   ugo::kern::SentCall* call = nullptr;    // device, [nconn], zero between calls
+  ugo::kern::SentCcCall* cc_call = nullptr;  // device, [nconn], zero between calls (ugo_fec_cc_sent_ack)
+  std::vector<ugo_cc_set*> cc_sets;       // the live controller sets that read its table
   uint32_t* chunk_member = nullptr;       // device, [nchunks], uploaded once
   int2* chunk_sum = nullptr;              // device, [nchunks]
   uint32_t* start_local = nullptr;        // device, [nconn]
@@ -3088,6 +3092,18 @@ struct ugo_sent_tx_set {
   size_t nchunks = 0;
   size_t min_seg_cap = 0;
   hipStream_t last = nullptr;             // the stream of the last call on the set
+  bool used = false;
+};
+
+// A set of congestion controllers (include/ugo_cc.h), one per member of a set of sent histories.
+struct ugo_cc_set {
+  ugo_fec* ctx = nullptr;
+  ugo_sent_tx_set* sent = nullptr;        // null once the sent set is gone: every call is then an argument error
+  ugo::kern::CcRecord* recs = nullptr;    // device, [nconn]
+  unsigned long long* cutback = nullptr;  // device, [nconn]
+  ugo_cc_params params{};
+  size_t nconn = 0;
+  hipStream_t last = nullptr;
   bool used = false;
 };
 
@@ -3189,11 +3205,13 @@ int sent_set_build(ugo_fec* c, ugo_sent_tx* const* txs, size_t nconn, ugo_sent_t
   if (hipMalloc(&set->table, nconn * sizeof(host[0])) != hipSuccess ||
       hipMalloc(&set->gathered, nconn * sizeof(ugo_sent_state)) != hipSuccess ||
       hipMalloc(&set->call, nconn * sizeof(ugo::kern::SentCall)) != hipSuccess ||
+      hipMalloc(&set->cc_call, nconn * sizeof(ugo::kern::SentCcCall)) != hipSuccess ||
       hipMalloc(&set->chunk_member, set->nchunks * sizeof(uint32_t)) != hipSuccess ||
       hipMalloc(&set->chunk_sum, set->nchunks * sizeof(int2)) != hipSuccess ||
       hipMalloc(&set->start_local, nconn * sizeof(uint32_t)) != hipSuccess ||
       hipMalloc(&set->words, nwords * sizeof(uint64_t)) != hipSuccess ||
       hipMemset(set->call, 0, nconn * sizeof(ugo::kern::SentCall)) != hipSuccess ||
+      hipMemset(set->cc_call, 0, nconn * sizeof(ugo::kern::SentCcCall)) != hipSuccess ||
       hipMemset(set->chunk_sum, 0, set->nchunks * sizeof(int2)) != hipSuccess ||
       hipMemset(set->start_local, 0, nconn * sizeof(uint32_t)) != hipSuccess ||
       hipMemset(set->words, 0, nwords * sizeof(uint64_t)) != hipSuccess ||
@@ -3232,9 +3250,14 @@ void ugo_fec_sent_set_destroy(ugo_sent_tx_set* set) {
   {
     DeviceGuard g(set->ctx->device);
     if (set->used) (void)hipStreamSynchronize(set->last);
+    for (ugo_cc_set* cs : set->cc_sets) {  // they read the table: wait for them, then they are closed
+      if (cs->used) (void)hipStreamSynchronize(cs->last);
+      cs->sent = nullptr;
+    }
     (void)hipFree(set->table);
     (void)hipFree(set->gathered);
     (void)hipFree(set->call);
+    (void)hipFree(set->cc_call);
     (void)hipFree(set->chunk_member);
     (void)hipFree(set->chunk_sum);
     (void)hipFree(set->start_local);
@@ -3276,14 +3299,16 @@ int ugo_fec_sent_set_record(ugo_sent_tx_set* set, const ugo_pkt_info* info, cons
   return hip_status(ugo::kern::launch_sent_record(a, set->last));
 }
 
-int ugo_fec_sent_set_ack(ugo_sent_tx_set* set, const ugo_pkt_info* info, const uint64_t* ranges, size_t max_ranges,
-                         const uint32_t* conn_of, size_t npk, uint64_t now_us, ugo_sent_event* events, void* stream) {
-  if (const int st = sent_enter(set)) return st;
-  if (!ugo::sentargs::ack_ok(info, ranges, max_ranges, conn_of, npk, events)) return UGO_FEC_ERR_INVALID_ARG;
+namespace {
+// The body of ugo_fec_sent_set_ack (split and rows null) and of ugo_fec_cc_sent_ack (include/ugo_cc.h).
+int sent_ack_body(ugo_sent_tx_set* set, const ugo_pkt_info* info, const uint64_t* ranges, size_t max_ranges,
+                  const uint32_t* conn_of, size_t npk, uint64_t now_us, ugo_sent_event* events, const uint64_t* split,
+                  ugo_cc_row* rows, void* stream) {
   ugo_fec* c = set->ctx;
   DeviceGuard g(c->device);
   if (!g.ok) return UGO_FEC_ERR_NO_DEVICE;
-  if (!device_view(info) || !device_view(ranges) || !device_view(conn_of) || !device_view(events))
+  if (!device_view(info) || !device_view(ranges) || !device_view(conn_of) || !device_view(events) ||
+      !device_view(split) || !device_view(rows))
     return UGO_FEC_ERR_INVALID_ARG;
   TimerScope ts(c);
   ugo::kern::SentAckArgs a{};
@@ -3295,6 +3320,9 @@ int ugo_fec_sent_set_ack(ugo_sent_tx_set* set, const ugo_pkt_info* info, const u
   a.ranges = ranges;
   a.conn_of = conn_of;
   a.events = events;
+  a.cc_call = set->cc_call;
+  a.split = reinterpret_cast<const unsigned long long*>(split);
+  a.rows = rows;
   a.npk = npk;
   a.now_us = now_us;
   a.nconn = static_cast<uint32_t>(set->members.size());
@@ -3303,6 +3331,14 @@ int ugo_fec_sent_set_ack(ugo_sent_tx_set* set, const ugo_pkt_info* info, const u
   set->last = static_cast<hipStream_t>(stream);
   set->used = true;
   return hip_status(ugo::kern::launch_sent_ack(a, set->last));
+}
+}  // namespace
+
+int ugo_fec_sent_set_ack(ugo_sent_tx_set* set, const ugo_pkt_info* info, const uint64_t* ranges, size_t max_ranges,
+                         const uint32_t* conn_of, size_t npk, uint64_t now_us, ugo_sent_event* events, void* stream) {
+  if (const int st = sent_enter(set)) return st;
+  if (!ugo::sentargs::ack_ok(info, ranges, max_ranges, conn_of, npk, events)) return UGO_FEC_ERR_INVALID_ARG;
+  return sent_ack_body(set, info, ranges, max_ranges, conn_of, npk, now_us, events, nullptr, nullptr, stream);
 }
 
 int ugo_fec_sent_set_rto(ugo_sent_tx_set* set, const uint64_t* delay_us, uint64_t now_us, uint8_t* fired,
@@ -3391,6 +3427,141 @@ int ugo_fec_sent_set_state(ugo_sent_tx_set* set, ugo_sent_state* host_out) {
       hipStreamSynchronize(set->last) != hipSuccess)
     return UGO_FEC_ERR_HIP;
   return hip_status(hipMemcpy(host_out, set->gathered, nconn * sizeof(*host_out), hipMemcpyDeviceToHost));
+}
+
+// ---------------------------------------------------------------- congestion control (include/ugo_cc.h)
+namespace {
+int cc_enter(ugo_cc_set* set) {
+  if (!set || !set->sent) return UGO_FEC_ERR_INVALID_ARG;
+  if (set->ctx->poisoned) return UGO_FEC_ERR_HIP;
+  return UGO_FEC_OK;
+}
+
+int cc_set_build(ugo_fec* c, ugo_sent_tx_set* sent, const ugo_cc_params& p, ugo_cc_set** out) {
+  DeviceGuard g(c->device);
+  if (!g.ok) return UGO_FEC_ERR_NO_DEVICE;
+  const std::vector<ugo_cc_state> init(sent->members.size(), ugo::ccargs::initial(p));
+  sent->cc_sets.reserve(sent->cc_sets.size() + 1);  // what may throw comes before the set exists
+  ugo_cc_set* set = new (std::nothrow) ugo_cc_set();
+  if (!set) return UGO_FEC_ERR_HIP;
+  set->ctx = c;
+  set->params = p;
+  set->nconn = init.size();
+  sent->cc_sets.push_back(set);
+  set->sent = sent;
+  if (hipMalloc(&set->recs, set->nconn * sizeof(ugo_cc_state)) != hipSuccess ||
+      hipMalloc(&set->cutback, set->nconn * sizeof(uint64_t)) != hipSuccess ||
+      hipMemset(set->cutback, 0, set->nconn * sizeof(uint64_t)) != hipSuccess ||
+      hipMemcpy(set->recs, init.data(), set->nconn * sizeof(ugo_cc_state), hipMemcpyHostToDevice) != hipSuccess ||
+      hipStreamSynchronize(nullptr) != hipSuccess) {
+    (void)hipGetLastError();
+    ugo_fec_cc_set_destroy(set);
+    return UGO_FEC_ERR_HIP;
+  }
+  *out = set;
+  return UGO_FEC_OK;
+}
+}  // namespace
+
+int ugo_fec_cc_set_create(ugo_fec* c, ugo_sent_tx_set* sent, const ugo_cc_params* params, ugo_cc_set** out) {
+  static_assert(sizeof(ugo_cc_state) == 192 && sizeof(ugo_cc_row) == 32 && sizeof(ugo_cc_params) == 20,
+                "the layouts ugo_cc.h states");
+  static_assert(UGO_FEC_KERNEL_CC == ugo::kern::kKCc, "kernel class matches sent_kernels.hpp");
+  if (out) *out = nullptr;
+  if (!c || !sent || !out || sent->ctx != c) return UGO_FEC_ERR_INVALID_ARG;
+  const ugo_cc_params p = params ? *params : ugo::ccargs::defaults();
+  if (!ugo::ccargs::params_ok(p)) return UGO_FEC_ERR_INVALID_ARG;
+  if (c->poisoned) return UGO_FEC_ERR_HIP;
+  try {
+    return cc_set_build(c, sent, p, out);
+  } catch (const std::bad_alloc&) {  // nothing throws through the C boundary
+    return UGO_FEC_ERR_HIP;
+  }
+}
+
+void ugo_fec_cc_set_destroy(ugo_cc_set* set) {
+  if (!set) return;
+  {
+    DeviceGuard g(set->ctx->device);
+    if (set->used) (void)hipStreamSynchronize(set->last);
+    (void)hipFree(set->recs);
+    (void)hipFree(set->cutback);
+  }
+  if (set->sent)
+    set->sent->cc_sets.erase(std::remove(set->sent->cc_sets.begin(), set->sent->cc_sets.end(), set),
+                             set->sent->cc_sets.end());
+  delete set;
+}
+
+int ugo_fec_cc_set_cutback(ugo_cc_set* set, const uint64_t** dev) {
+  if (!set || !dev) return UGO_FEC_ERR_INVALID_ARG;
+  *dev = reinterpret_cast<const uint64_t*>(set->cutback);
+  return UGO_FEC_OK;
+}
+
+int ugo_fec_cc_sent_ack(ugo_sent_tx_set* set, const ugo_pkt_info* info, const uint64_t* ranges, size_t max_ranges,
+                        const uint32_t* conn_of, size_t npk, uint64_t now_us, ugo_sent_event* events,
+                        const uint64_t* split, ugo_cc_row* rows, void* stream) {
+  if (const int st = sent_enter(set)) return st;
+  if (!ugo::ccargs::sent_ack_ok(info, ranges, max_ranges, conn_of, npk, events, split, rows))
+    return UGO_FEC_ERR_INVALID_ARG;
+  return sent_ack_body(set, info, ranges, max_ranges, conn_of, npk, now_us, events, split, rows, stream);
+}
+
+int ugo_fec_cc_set_ack(ugo_cc_set* set, const ugo_sent_event* events, const ugo_cc_row* rows, uint64_t now_us,
+                       uint64_t* delay_us, void* stream) {
+  if (const int st = cc_enter(set)) return st;
+  if (!ugo::ccargs::ack_ok(events, rows, delay_us)) return UGO_FEC_ERR_INVALID_ARG;
+  ugo_fec* c = set->ctx;
+  DeviceGuard g(c->device);
+  if (!g.ok) return UGO_FEC_ERR_NO_DEVICE;
+  if (!device_view(events) || !device_view(rows) || !device_view(delay_us)) return UGO_FEC_ERR_INVALID_ARG;
+  TimerScope ts(c);
+  ugo::kern::CcAckArgs a{};
+  a.table = set->sent->table;
+  a.recs = set->recs;
+  a.cutback = set->cutback;
+  a.events = events;
+  a.rows = rows;
+  a.delay_us = reinterpret_cast<unsigned long long*>(delay_us);
+  a.now_us = now_us;
+  a.p = set->params;
+  a.nconn = static_cast<uint32_t>(set->nconn);
+  set->last = static_cast<hipStream_t>(stream);
+  set->used = true;
+  return hip_status(ugo::kern::launch_cc_ack(a, set->last));
+}
+
+int ugo_fec_cc_set_rto(ugo_cc_set* set, const uint8_t* fired, size_t packet_bytes, size_t max_budget,
+                       uint32_t* budget, void* stream) {
+  if (const int st = cc_enter(set)) return st;
+  if (!ugo::ccargs::rto_ok(fired, packet_bytes, max_budget, budget)) return UGO_FEC_ERR_INVALID_ARG;
+  ugo_fec* c = set->ctx;
+  DeviceGuard g(c->device);
+  if (!g.ok) return UGO_FEC_ERR_NO_DEVICE;
+  if (!device_view(fired) || !device_view(budget)) return UGO_FEC_ERR_INVALID_ARG;
+  TimerScope ts(c);
+  ugo::kern::CcRtoArgs a{};
+  a.table = set->sent->table;
+  a.recs = set->recs;
+  a.cutback = set->cutback;
+  a.fired = fired;
+  a.budget = budget;
+  a.packet_bytes = packet_bytes;
+  a.max_budget = max_budget;
+  a.p = set->params;
+  a.nconn = static_cast<uint32_t>(set->nconn);
+  set->last = static_cast<hipStream_t>(stream);
+  set->used = true;
+  return hip_status(ugo::kern::launch_cc_rto(a, set->last));
+}
+
+int ugo_fec_cc_set_state(ugo_cc_set* set, ugo_cc_state* host_out) {
+  if (!set || !host_out) return UGO_FEC_ERR_INVALID_ARG;
+  DeviceGuard g(set->ctx->device);
+  if (!g.ok) return UGO_FEC_ERR_NO_DEVICE;
+  if (set->used && hipStreamSynchronize(set->last) != hipSuccess) return UGO_FEC_ERR_HIP;
+  return hip_status(hipMemcpy(host_out, set->recs, set->nconn * sizeof(*host_out), hipMemcpyDeviceToHost));
 }
 
 int ugo_fec_rc4_keystream(const uint8_t* key, size_t key_len, uint8_t* out, size_t n) {

@@ -45,6 +45,7 @@ PKT_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ugo_pkt.h")
 STREAM_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ugo_stream.h")
 ACK_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ugo_ack.h")
 SENT_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ugo_sent.h")
+CC_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ugo_cc.h")
 
 OK = 0
 RECONSTRUCT_DATA_ONLY = 1
@@ -109,7 +110,7 @@ PKT_INFO_DTYPE = np.dtype([("packet_number", "<u8"), ("stop_waiting", "<u8"), ("
 # include/ugo_fec.h launch timing
 KERNEL_NAMES = {1: "encode", 2: "reconstruct", 3: "prepare", 4: "bytes", 5: "rx_assemble", 6: "tx_assemble",
                 7: "packet_decode", 8: "packet_encode", 9: "stream_deliver", 10: "stream_read", 11: "stream_tx",
-                12: "ack", 13: "sent"}
+                12: "ack", 13: "sent", 14: "cc"}
 KERNEL_IDS = {v: k for k, v in KERNEL_NAMES.items()}
 LAUNCH_TIME_DTYPE = np.dtype([("kernel", "<u4"), ("ms", "<f4")])
 PKT_SEGMENT_DTYPE = np.dtype([("offset", "<u8"), ("data_off", "<u4"), ("len", "<u2"), ("avail", "<u2")])
@@ -178,6 +179,23 @@ SENT_EVENT_DTYPE = np.dtype([("rtt_us", "<u8"), ("delay_us", "<u8"), ("acked_byt
                              ("reserved", "u1", (6,))])
 assert SENT_SLOT_DTYPE.itemsize == 32 and SENT_SEG_DTYPE.itemsize == 16
 assert SENT_STATE_DTYPE.itemsize == 160 and SENT_EVENT_DTYPE.itemsize == 64
+
+# include/ugo_cc.h, congestion control
+CC_MAX_CWND_LIMIT = 1 << 20
+CC_DEFAULTS = dict(initial_cwnd=32, max_cwnd=200, min_cwnd=2, num_connections=2, mss=1460)
+CC_PARAMS_DTYPE = np.dtype([("initial_cwnd", "<u4"), ("max_cwnd", "<u4"), ("min_cwnd", "<u4"),
+                            ("num_connections", "<u4"), ("mss", "<u4")])
+CC_ROW_DTYPE = np.dtype([("max_lost", "<u8"), ("max_acked", "<u8"), ("acked_le", "<u4"), ("reserved", "u1", (12,))])
+CC_STATE_DTYPE = np.dtype([("cwnd", "<u8"), ("ssthresh", "<u8"), ("largest_acked", "<u8"), ("cutback", "<u8"),
+                           ("min_rtt_us", "<u8"), ("latest_rtt_us", "<u8"), ("srtt_us", "<u8"),
+                           ("mean_dev_us", "<u8"), ("end_packet_number", "<u8"), ("current_min_rtt_us", "<u8"),
+                           ("epoch_us", "<u8"), ("app_limited_us", "<u8"), ("last_update_us", "<u8"),
+                           ("last_cwnd", "<u8"), ("last_max_cwnd", "<u8"), ("est_tcp_cwnd", "<u8"),
+                           ("origin_cwnd", "<u8"), ("last_target_cwnd", "<u8"), ("rto_candidate", "<u8"),
+                           ("cutbacks", "<u8"), ("rtos", "<u8"), ("sample_count", "<u4"), ("acked_count", "<u4"),
+                           ("time_to_origin", "<u4"), ("last_cutback_exited_slowstart", "u1"), ("started", "u1"),
+                           ("found", "u1"), ("reserved", "u1", (9,))])
+assert CC_PARAMS_DTYPE.itemsize == 20 and CC_ROW_DTYPE.itemsize == 32 and CC_STATE_DTYPE.itemsize == 192
 
 
 def load_library(path: str = LIB_PATH):
@@ -272,6 +290,14 @@ def load_library(path: str = LIB_PATH):
     lib.ugo_fec_sent_set_drain.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, vp]
     lib.ugo_fec_sent_set_attach.argtypes = [vp, vp, vp, sz, vp, vp, vp]
     lib.ugo_fec_sent_set_state.argtypes = [vp, vp]
+    lib.ugo_fec_cc_set_create.argtypes = [vp, vp, vp, ctypes.POINTER(vp)]
+    lib.ugo_fec_cc_set_destroy.argtypes = [vp]
+    lib.ugo_fec_cc_set_destroy.restype = None
+    lib.ugo_fec_cc_set_cutback.argtypes = [vp, ctypes.POINTER(vp)]
+    lib.ugo_fec_cc_sent_ack.argtypes = [vp, vp, vp, sz, vp, sz, u64, vp, vp, vp, vp]
+    lib.ugo_fec_cc_set_ack.argtypes = [vp, vp, vp, u64, vp, vp]
+    lib.ugo_fec_cc_set_rto.argtypes = [vp, vp, sz, sz, vp, vp]
+    lib.ugo_fec_cc_set_state.argtypes = [vp, vp]
     lib.ugo_fec_reconstruct_rows.argtypes = [vp, vp, vp, sz, sz, vp, sz, sz, u, vp, vp]
     lib.ugo_fec_lossy_groups.argtypes = [vp, vp, sz, u, vp, vp, vp]
     lib.ugo_fec_rx_recover_host.argtypes = [vp, vp, sz, vp, sz, vp, ctypes.c_uint64, sz, sz, vp, vp, vp, sz, sz, vp,
@@ -289,9 +315,9 @@ def load_library(path: str = LIB_PATH):
 
 
 def header_symbols(paths=(HEADER_PATH, CONN_HEADER_PATH, PKT_HEADER_PATH, STREAM_HEADER_PATH,
-                          ACK_HEADER_PATH, SENT_HEADER_PATH)) -> List[str]:
-    """Every entry point declared in include/ugo_fec.h, ugo_fec_conn.h, ugo_pkt.h, ugo_stream.h, ugo_ack.h and
-    ugo_sent.h."""
+                          ACK_HEADER_PATH, SENT_HEADER_PATH, CC_HEADER_PATH)) -> List[str]:
+    """Every entry point declared in include/ugo_fec.h, ugo_fec_conn.h, ugo_pkt.h, ugo_stream.h, ugo_ack.h,
+    ugo_sent.h and ugo_cc.h."""
     out = set()
     for path in paths:
         src = open(path).read()
@@ -1459,6 +1485,7 @@ class SentTxSet:
         for tx in txs:
             tx._sets.add(self)
         self.device = enc.device
+        self._cc_sets = weakref.WeakSet()  # the open controller sets that read it: closed before it
 
     @staticmethod
     def check_members(enc, txs):
@@ -1483,6 +1510,8 @@ class SentTxSet:
 
     def close(self):
         if getattr(self, "_h", None):
+            for s in list(getattr(self, "_cc_sets", ())):
+                s.close()
             load_library().ugo_fec_sent_set_destroy(self._h)
             self._h = None
 
@@ -1587,6 +1616,118 @@ class SentTxSet:
         """The members' records (SENT_STATE_DTYPE [nconn]); waits for the last call on the set."""
         out = np.zeros(self.nconn, SENT_STATE_DTYPE)
         _raise(load_library().ugo_fec_sent_set_state(self._h, out.ctypes.data))
+        return out
+
+
+class CcSet:
+    """The congestion controllers of a SentTxSet's members (include/ugo_cc.h):
+    RTT filter, hybrid slow start and CUBIC, one record per member.  Per batch:
+    sent_ack in place of SentTxSet.ack, ack, SentTxSet.rto with the delays ack
+    returned, rto, and the next StreamTxSet.plan with the budget rto returned.
+    Operands are tensors in device or pinned host memory; nothing is
+    synchronised but states().  Close it before the SentTxSet."""
+
+    def __init__(self, enc: Encoder, sent: "SentTxSet", **params):
+        p = self.check_params(**params)
+        _require(isinstance(sent, SentTxSet) and getattr(sent, "_h", None) and sent._enc is enc,
+                 "sent must be an open SentTxSet of the same context")
+        arr = np.array([tuple(p[k] for k in CC_PARAMS_DTYPE.names)], CC_PARAMS_DTYPE)
+        h = ctypes.c_void_p()
+        _raise(load_library().ugo_fec_cc_set_create(enc._h, sent._h, arr.ctypes.data if params else None,
+                                                    ctypes.byref(h)))
+        self._h, self._enc, self.sent = h, enc, sent  # context and sent set must outlive the set
+        self.nconn, self.params, self.device = sent.nconn, p, enc.device
+        sent._cc_sets.add(self)
+
+    @staticmethod
+    def check_params(**params):
+        _require(set(params) <= set(CC_DEFAULTS), f"parameters are {sorted(CC_DEFAULTS)}")
+        p = dict(CC_DEFAULTS, **params)
+        _require(all(isinstance(v, int) and 0 <= v < 1 << 32 for v in p.values()))
+        _require(1 <= p["min_cwnd"] <= p["initial_cwnd"] <= p["max_cwnd"] <= CC_MAX_CWND_LIMIT,
+                 "1 <= min_cwnd <= initial_cwnd <= max_cwnd <= 2^20")
+        _require(p["num_connections"] >= 1 and p["mss"] >= 1, "num_connections and mss must be at least 1")
+        return p
+
+    def close(self):
+        if getattr(self, "_h", None):
+            load_library().ugo_fec_cc_set_destroy(self._h)
+            self._h = None
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _dev(self):
+        return torch.device("cuda", self.device)
+
+    def cutback(self):
+        """ugo_fec_cc_set_cutback: the dense cutback array as an int64 CUDA tensor
+        [nconn] over the device memory itself: what sent_ack takes as split."""
+        p = ctypes.c_void_p()
+        _raise(load_library().ugo_fec_cc_set_cutback(self._h, ctypes.byref(p)))
+        t = torch.as_tensor(_DeviceBytes(p.value, self.nconn * 8, self), device=self._dev())
+        return t.view(torch.int64)
+
+    def sent_ack(self, info, ranges, conn_of, now_us: int, npackets: Optional[int] = None, events=None, split=None,
+                 rows=None, stream=None):
+        """ugo_fec_cc_sent_ack: SentTxSet.ack, and rows uint8 [nconn, 32]
+        (CC_ROW_DTYPE) beside events.  split int64 [nconn]; None: the set's own
+        cutback array.  Returns (events, rows)."""
+        sent = self.sent
+        npk = info.shape[0] if npackets is None else npackets
+        sent._check_info(info, npk)
+        _require(0 <= now_us < 1 << 64)
+        _require(ranges.is_contiguous() and ranges.element_size() == 8 and ranges.dim() == 3 and
+                 ranges.shape[0] >= npk and ranges.shape[1] <= 0xffff and ranges.shape[2] == 2)
+        sent._check_list(conn_of, npk, 4, "conn_of")
+        if events is None:
+            events = torch.zeros((self.nconn, 64), dtype=torch.uint8, device=self._dev())
+        if rows is None:
+            rows = torch.zeros((self.nconn, 32), dtype=torch.uint8, device=self._dev())
+        if split is None:
+            split = self.cutback()
+        _require(events.is_contiguous() and events.element_size() == 1 and tuple(events.shape) == (self.nconn, 64))
+        _require(rows.is_contiguous() and rows.element_size() == 1 and tuple(rows.shape) == (self.nconn, 32))
+        sent.check_per_conn(split, 8, "split")
+        _raise(load_library().ugo_fec_cc_sent_ack(
+            sent._h, info.data_ptr(), ranges.data_ptr() if ranges.numel() else None, ranges.shape[1],
+            conn_of.data_ptr(), npk, now_us, events.data_ptr(), split.data_ptr(), rows.data_ptr(),
+            _stream_handle(stream)))
+        return events, rows
+
+    def ack(self, events, rows, now_us: int, delay_us=None, stream=None):
+        """ugo_fec_cc_set_ack: events uint8 [nconn, 64] and rows uint8 [nconn, 32]
+        as sent_ack returned them.  Returns delay_us int64 [nconn]: the input of
+        SentTxSet.rto."""
+        _require(0 <= now_us < 1 << 64)
+        _require(events.is_contiguous() and events.element_size() == 1 and tuple(events.shape) == (self.nconn, 64))
+        _require(rows.is_contiguous() and rows.element_size() == 1 and tuple(rows.shape) == (self.nconn, 32))
+        if delay_us is None:
+            delay_us = torch.zeros(self.nconn, dtype=torch.int64, device=self._dev())
+        self.sent.check_per_conn(delay_us, 8, "delay_us")
+        _raise(load_library().ugo_fec_cc_set_ack(self._h, events.data_ptr(), rows.data_ptr(), now_us,
+                                                 delay_us.data_ptr(), _stream_handle(stream)))
+        return delay_us
+
+    def rto(self, fired, packet_bytes: int, max_budget: int, budget=None, stream=None):
+        """ugo_fec_cc_set_rto: fired uint8 [nconn] as SentTxSet.rto returned it.
+        Returns budget int32 [nconn]: the input of StreamTxSet.plan."""
+        _require(packet_bytes >= 1 and 0 <= max_budget <= 1 << 31)
+        self.sent.check_per_conn(fired, 1, "fired")
+        if budget is None:
+            budget = torch.zeros(self.nconn, dtype=torch.int32, device=self._dev())
+        self.sent.check_per_conn(budget, 4, "budget")
+        _raise(load_library().ugo_fec_cc_set_rto(self._h, fired.data_ptr(), packet_bytes, max_budget,
+                                                 budget.data_ptr(), _stream_handle(stream)))
+        return budget
+
+    def states(self) -> np.ndarray:
+        """The members' records (CC_STATE_DTYPE [nconn]); waits for the last call on the set."""
+        out = np.zeros(self.nconn, CC_STATE_DTYPE)
+        _raise(load_library().ugo_fec_cc_set_state(self._h, out.ctypes.data))
         return out
 
 

@@ -70,7 +70,9 @@ extern "C" {
  *    the receive histories, ugo_fec_ack_* (ugo_ack.h), with UGO_FEC_KERNEL_ACK
  *    (12, defined there); the sent histories, ugo_fec_sent_* (ugo_sent.h), with
  *    UGO_FEC_KERNEL_SENT (13, defined there); congestion control,
- *    ugo_fec_cc_* (ugo_cc.h), with UGO_FEC_KERNEL_CC (14, defined there). */
+ *    ugo_fec_cc_* (ugo_cc.h), with UGO_FEC_KERNEL_CC (14, defined there); the
+ *    connection table, ugo_fec_listen_* (ugo_listen.h), with
+ *    UGO_FEC_KERNEL_LISTEN (15, defined there). */
 #define UGO_FEC_ABI_VERSION 9
 
 /* Status codes.  1..5 map 1:1 onto the klauspost/reedsolomon error values

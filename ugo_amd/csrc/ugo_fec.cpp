@@ -38,6 +38,8 @@
 #include "host/cc_args.hpp"
 #include "host/sent_args.hpp"
 #include "cc_kernels.hpp"
+#include "host/listen_args.hpp"
+#include "listen_kernels.hpp"
 #include "sent_kernels.hpp"
 
 namespace {
@@ -3562,6 +3564,169 @@ int ugo_fec_cc_set_state(ugo_cc_set* set, ugo_cc_state* host_out) {
   if (!g.ok) return UGO_FEC_ERR_NO_DEVICE;
   if (set->used && hipStreamSynchronize(set->last) != hipSuccess) return UGO_FEC_ERR_HIP;
   return hip_status(hipMemcpy(host_out, set->recs, set->nconn * sizeof(*host_out), hipMemcpyDeviceToHost));
+}
+
+// ---------------------------------------------------------------- connection table (include/ugo_listen.h)
+struct ugo_listen_table {
+  ugo_fec* ctx = nullptr;
+  ugo::kern::ListenTable t{};  // every array of it is the table's own
+  hipStream_t last = nullptr;  // the stream of the last call on the table
+  bool used = false;
+};
+
+namespace {
+int listen_enter(ugo_listen_table* table) {
+  if (!table) return UGO_FEC_ERR_INVALID_ARG;
+  if (table->ctx->poisoned) return UGO_FEC_ERR_HIP;
+  return UGO_FEC_OK;
+}
+}  // namespace
+
+int ugo_fec_listen_create(ugo_fec* c, size_t max_conn, ugo_listen_table** out) {
+  static_assert(sizeof(ugo_listen_state) == 80 && sizeof(ugo_listen_accept) == 48 && sizeof(ugo_listen_entry) == 32,
+                "the layouts ugo_listen.h states");
+  static_assert(UGO_FEC_KERNEL_LISTEN == ugo::kern::kKListen, "kernel class matches listen_kernels.hpp");
+  if (out) *out = nullptr;
+  if (!c || !out || !ugo::listenargs::max_conn_ok(max_conn)) return UGO_FEC_ERR_INVALID_ARG;
+  if (c->poisoned) return UGO_FEC_ERR_HIP;
+  DeviceGuard g(c->device);
+  if (!g.ok) return UGO_FEC_ERR_NO_DEVICE;
+  ugo_listen_table* table = new (std::nothrow) ugo_listen_table();
+  if (!table) return UGO_FEC_ERR_HIP;
+  table->ctx = c;
+  ugo::kern::ListenTable& t = table->t;
+  t.max_conn = static_cast<uint32_t>(max_conn);
+  t.n_slots = ugo::listenargs::slots_for(max_conn);
+  if (hipMalloc(&t.slots, size_t(t.n_slots) * sizeof(ugo::kern::ListenSlot)) != hipSuccess ||
+      hipMalloc(&t.claim, size_t(t.n_slots) * sizeof(uint32_t)) != hipSuccess ||
+      hipMalloc(&t.names, max_conn * UGO_LISTEN_NAME_BYTES) != hipSuccess ||
+      hipMalloc(&t.tmp_names, max_conn * UGO_LISTEN_NAME_BYTES) != hipSuccess ||
+      hipMalloc(&t.member_slot, max_conn * sizeof(uint32_t)) != hipSuccess ||
+      hipMalloc(&t.mark, max_conn * sizeof(uint32_t)) != hipSuccess ||
+      hipMalloc(&t.block_count, ugo::kern::kListenScanBlocks * sizeof(uint32_t)) != hipSuccess ||
+      hipMalloc(&t.st, sizeof(ugo_listen_state)) != hipSuccess ||
+      hipMalloc(&t.call, sizeof(ugo::kern::ListenCall)) != hipSuccess ||
+      hipMemset(t.tmp_names, 0, max_conn * UGO_LISTEN_NAME_BYTES) != hipSuccess ||
+      hipMemset(t.block_count, 0, ugo::kern::kListenScanBlocks * sizeof(uint32_t)) != hipSuccess ||
+      ugo::kern::launch_listen_init(t, nullptr) != hipSuccess || hipStreamSynchronize(nullptr) != hipSuccess) {
+    (void)hipGetLastError();
+    ugo_fec_listen_destroy(table);
+    return UGO_FEC_ERR_HIP;
+  }
+  *out = table;
+  return UGO_FEC_OK;
+}
+
+void ugo_fec_listen_destroy(ugo_listen_table* table) {
+  if (!table) return;
+  {
+    DeviceGuard g(table->ctx->device);
+    if (table->used) (void)hipStreamSynchronize(table->last);
+    ugo::kern::ListenTable& t = table->t;
+    (void)hipFree(t.slots);
+    (void)hipFree(t.claim);
+    (void)hipFree(t.names);
+    (void)hipFree(t.tmp_names);
+    (void)hipFree(t.member_slot);
+    (void)hipFree(t.mark);
+    (void)hipFree(t.block_count);
+    (void)hipFree(t.st);
+    (void)hipFree(t.call);
+  }
+  delete table;
+}
+
+int ugo_fec_listen_state(ugo_listen_table* table, ugo_listen_state* host_out) {
+  if (!table || !host_out) return UGO_FEC_ERR_INVALID_ARG;
+  DeviceGuard g(table->ctx->device);
+  if (!g.ok) return UGO_FEC_ERR_NO_DEVICE;
+  if (table->used && hipStreamSynchronize(table->last) != hipSuccess) return UGO_FEC_ERR_HIP;
+  return hip_status(hipMemcpy(host_out, table->t.st, sizeof(*host_out), hipMemcpyDeviceToHost));
+}
+
+int ugo_fec_listen_route(ugo_listen_table* table, const uint8_t* names, const uint8_t* pkts, size_t slot,
+                         const uint16_t* lens, size_t npk, uint32_t* conn_of, uint8_t* cls,
+                         ugo_listen_accept* accepted, size_t max_accepted, uint32_t* n_accepted, void* stream) {
+  if (const int st = listen_enter(table)) return st;
+  if (npk == 0) return UGO_FEC_OK;
+  if (!ugo::listenargs::route_ok(names, pkts, slot, lens, npk, conn_of, cls, accepted, max_accepted, n_accepted))
+    return UGO_FEC_ERR_INVALID_ARG;
+  ugo_fec* c = table->ctx;
+  DeviceGuard g(c->device);
+  if (!g.ok) return UGO_FEC_ERR_NO_DEVICE;
+  if (!device_view(names) || !device_view(pkts) || !device_view(lens) || !device_view(conn_of) ||
+      !device_view(cls) || !device_view(accepted) || !device_view(n_accepted))
+    return UGO_FEC_ERR_INVALID_ARG;
+  TimerScope ts(c);
+  ugo::kern::ListenRouteArgs a{};
+  a.t = table->t;
+  a.names = names;
+  a.pkts = pkts;
+  a.lens = lens;
+  a.conn_of = conn_of;
+  a.cls = cls;
+  a.accepted = accepted;
+  a.n_accepted = n_accepted;
+  a.slot = static_cast<uint32_t>(slot);
+  a.npackets = static_cast<uint32_t>(npk);
+  a.max_accepted = static_cast<uint32_t>(max_accepted);
+  table->last = static_cast<hipStream_t>(stream);
+  table->used = true;
+  return hip_status(ugo::kern::launch_listen_route(a, table->last));
+}
+
+int ugo_fec_listen_remap(ugo_listen_table* table, const uint32_t* new_index, size_t n_index, size_t nconn_new,
+                         uint32_t* status, void* stream) {
+  if (const int st = listen_enter(table)) return st;
+  if (!ugo::listenargs::remap_ok(new_index, n_index, nconn_new, status)) return UGO_FEC_ERR_INVALID_ARG;
+  ugo_fec* c = table->ctx;
+  DeviceGuard g(c->device);
+  if (!g.ok) return UGO_FEC_ERR_NO_DEVICE;
+  if (!device_view(new_index) || !device_view(status)) return UGO_FEC_ERR_INVALID_ARG;
+  TimerScope ts(c);
+  ugo::kern::ListenRemapArgs a{};
+  a.t = table->t;
+  a.new_index = new_index;
+  a.status = status;
+  a.n_index = static_cast<uint32_t>(n_index);
+  a.nconn_new = static_cast<uint32_t>(std::min<size_t>(nconn_new, size_t(table->t.max_conn) + 1));
+  table->last = static_cast<hipStream_t>(stream);
+  table->used = true;
+  return hip_status(ugo::kern::launch_listen_remap(a, table->last));
+}
+
+int ugo_fec_listen_names(ugo_listen_table* table, const uint32_t* conn_of, size_t npk, uint8_t* names_out,
+                         uint32_t* name_lens, void* stream) {
+  if (const int st = listen_enter(table)) return st;
+  if (npk == 0) return UGO_FEC_OK;
+  if (!ugo::listenargs::names_ok(conn_of, npk, names_out, name_lens)) return UGO_FEC_ERR_INVALID_ARG;
+  ugo_fec* c = table->ctx;
+  DeviceGuard g(c->device);
+  if (!g.ok) return UGO_FEC_ERR_NO_DEVICE;
+  if (!device_view(conn_of) || !device_view(names_out) || !device_view(name_lens)) return UGO_FEC_ERR_INVALID_ARG;
+  TimerScope ts(c);
+  ugo::kern::ListenNamesArgs a{};
+  a.t = table->t;
+  a.conn_of = conn_of;
+  a.names_out = names_out;
+  a.name_lens = name_lens;
+  a.npackets = static_cast<uint32_t>(npk);
+  table->last = static_cast<hipStream_t>(stream);
+  table->used = true;
+  return hip_status(ugo::kern::launch_listen_names(a, table->last));
+}
+
+int ugo_fec_listen_entries(ugo_listen_table* table, ugo_listen_entry* out, size_t cap, void* stream) {
+  if (const int st = listen_enter(table)) return st;
+  if (!ugo::listenargs::entries_ok(out, cap)) return UGO_FEC_ERR_INVALID_ARG;
+  ugo_fec* c = table->ctx;
+  DeviceGuard g(c->device);
+  if (!g.ok) return UGO_FEC_ERR_NO_DEVICE;
+  if (!device_view(out)) return UGO_FEC_ERR_INVALID_ARG;
+  TimerScope ts(c);
+  table->last = static_cast<hipStream_t>(stream);
+  table->used = true;
+  return hip_status(ugo::kern::launch_listen_entries(table->t, out, static_cast<uint32_t>(cap), table->last));
 }
 
 int ugo_fec_rc4_keystream(const uint8_t* key, size_t key_len, uint8_t* out, size_t n) {

@@ -46,6 +46,7 @@ STREAM_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ugo_stream
 ACK_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ugo_ack.h")
 SENT_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ugo_sent.h")
 CC_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ugo_cc.h")
+LISTEN_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ugo_listen.h")
 
 OK = 0
 RECONSTRUCT_DATA_ONLY = 1
@@ -110,7 +111,7 @@ PKT_INFO_DTYPE = np.dtype([("packet_number", "<u8"), ("stop_waiting", "<u8"), ("
 # include/ugo_fec.h launch timing
 KERNEL_NAMES = {1: "encode", 2: "reconstruct", 3: "prepare", 4: "bytes", 5: "rx_assemble", 6: "tx_assemble",
                 7: "packet_decode", 8: "packet_encode", 9: "stream_deliver", 10: "stream_read", 11: "stream_tx",
-                12: "ack", 13: "sent", 14: "cc"}
+                12: "ack", 13: "sent", 14: "cc", 15: "listen"}
 KERNEL_IDS = {v: k for k, v in KERNEL_NAMES.items()}
 LAUNCH_TIME_DTYPE = np.dtype([("kernel", "<u4"), ("ms", "<f4")])
 PKT_SEGMENT_DTYPE = np.dtype([("offset", "<u8"), ("data_off", "<u4"), ("len", "<u2"), ("avail", "<u2")])
@@ -196,6 +197,22 @@ CC_STATE_DTYPE = np.dtype([("cwnd", "<u8"), ("ssthresh", "<u8"), ("largest_acked
                            ("time_to_origin", "<u4"), ("last_cutback_exited_slowstart", "u1"), ("started", "u1"),
                            ("found", "u1"), ("reserved", "u1", (9,))])
 assert CC_PARAMS_DTYPE.itemsize == 20 and CC_ROW_DTYPE.itemsize == 32 and CC_STATE_DTYPE.itemsize == 192
+# ugo_listen.h
+LISTEN_MAX_CONN = 1 << 20
+LISTEN_NAME_BYTES = 32
+LISTEN_FED, LISTEN_FED_NEW, LISTEN_DUP_INIT, LISTEN_ACCEPT = 0, 1, 2, 3
+LISTEN_STRANGER, LISTEN_REFUSED, LISTEN_BAD_NAME = 4, 5, 6
+LISTEN_NCLASS = 8
+LISTEN_FULL = 1  # ugo_listen_state.err
+LISTEN_REMAP_NOT_INJECTIVE, LISTEN_REMAP_OUT_OF_RANGE, LISTEN_REMAP_TOO_MANY, LISTEN_REMAP_LENGTH = 1, 2, 4, 8
+LISTEN_ACCEPT_DTYPE = np.dtype([("packet", "<u4"), ("member", "<u4"), ("client_id", "<u4"), ("reserved", "<u4"),
+                                ("name", "u1", (32,))])
+LISTEN_STATE_DTYPE = np.dtype([("nconn", "<u4"), ("n_dead", "<u4"), ("n_slots", "<u4"), ("err", "<u4"),
+                               ("counts", "<u8", (8,))])
+LISTEN_ENTRY_DTYPE = np.dtype([("ip", "u1", (16,)), ("scope", "<u4"), ("port", "<u4"), ("member", "<u4"),
+                               ("reserved", "<u4")])
+assert (LISTEN_ACCEPT_DTYPE.itemsize == 48 and LISTEN_STATE_DTYPE.itemsize == 80 and
+        LISTEN_ENTRY_DTYPE.itemsize == 32)
 
 
 def load_library(path: str = LIB_PATH):
@@ -298,6 +315,14 @@ def load_library(path: str = LIB_PATH):
     lib.ugo_fec_cc_set_ack.argtypes = [vp, vp, vp, u64, vp, vp]
     lib.ugo_fec_cc_set_rto.argtypes = [vp, vp, sz, sz, vp, vp]
     lib.ugo_fec_cc_set_state.argtypes = [vp, vp]
+    lib.ugo_fec_listen_create.argtypes = [vp, sz, ctypes.POINTER(vp)]
+    lib.ugo_fec_listen_destroy.argtypes = [vp]
+    lib.ugo_fec_listen_destroy.restype = None
+    lib.ugo_fec_listen_state.argtypes = [vp, vp]
+    lib.ugo_fec_listen_route.argtypes = [vp, vp, vp, sz, vp, sz, vp, vp, vp, sz, vp, vp]
+    lib.ugo_fec_listen_remap.argtypes = [vp, vp, sz, sz, vp, vp]
+    lib.ugo_fec_listen_names.argtypes = [vp, vp, sz, vp, vp, vp]
+    lib.ugo_fec_listen_entries.argtypes = [vp, vp, sz, vp]
     lib.ugo_fec_reconstruct_rows.argtypes = [vp, vp, vp, sz, sz, vp, sz, sz, u, vp, vp]
     lib.ugo_fec_lossy_groups.argtypes = [vp, vp, sz, u, vp, vp, vp]
     lib.ugo_fec_rx_recover_host.argtypes = [vp, vp, sz, vp, sz, vp, ctypes.c_uint64, sz, sz, vp, vp, vp, sz, sz, vp,
@@ -315,9 +340,9 @@ def load_library(path: str = LIB_PATH):
 
 
 def header_symbols(paths=(HEADER_PATH, CONN_HEADER_PATH, PKT_HEADER_PATH, STREAM_HEADER_PATH,
-                          ACK_HEADER_PATH, SENT_HEADER_PATH, CC_HEADER_PATH)) -> List[str]:
+                          ACK_HEADER_PATH, SENT_HEADER_PATH, CC_HEADER_PATH, LISTEN_HEADER_PATH)) -> List[str]:
     """Every entry point declared in include/ugo_fec.h, ugo_fec_conn.h, ugo_pkt.h, ugo_stream.h, ugo_ack.h,
-    ugo_sent.h and ugo_cc.h."""
+    ugo_sent.h, ugo_cc.h and ugo_listen.h."""
     out = set()
     for path in paths:
         src = open(path).read()
@@ -1729,6 +1754,120 @@ class CcSet:
         out = np.zeros(self.nconn, CC_STATE_DTYPE)
         _raise(load_library().ugo_fec_cc_set_state(self._h, out.ctypes.data))
         return out
+
+
+class ListenTable:
+    """The connection table of a listening socket (include/ugo_listen.h):
+    listener.handlePacket for a whole ring per call.  route writes conn_of for
+    the stages that take it and the list of accepted connections; names turns
+    the conn_of of StreamTxSet.plan into sendmmsg names; remap goes with a set
+    rebuild.  Operands are tensors in device or pinned host memory; nothing is
+    synchronised but state() and entries()."""
+
+    def __init__(self, enc: "Encoder", max_conn: int):
+        _require(isinstance(max_conn, int) and 1 <= max_conn <= LISTEN_MAX_CONN, "1 <= max_conn <= 2^20")
+        h = ctypes.c_void_p()
+        _raise(load_library().ugo_fec_listen_create(enc._h, max_conn, ctypes.byref(h)))
+        self._h, self._enc = h, enc  # the context must outlive the table
+        self.max_conn, self.device = max_conn, enc.device
+
+    def close(self):
+        if getattr(self, "_h", None):
+            load_library().ugo_fec_listen_destroy(self._h)
+            self._h = None
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _dev(self):
+        return torch.device("cuda", self.device)
+
+    @staticmethod
+    def _check(t, n, item, what, row=None):
+        shape = (n,) if row is None else (n, row)
+        _require(t.is_contiguous() and t.element_size() == item and t.dim() == len(shape) and t.shape[0] >= n and
+                 tuple(t.shape[1:]) == shape[1:], f"{what} must be contiguous, {item}-byte, at least {shape}")
+
+    def route(self, names, pkts, lens, npackets: Optional[int] = None, conn_of=None, cls=None, accepted=None,
+              n_accepted=None, stream=None):
+        """ugo_fec_listen_route.  names uint8 [npackets, 32], pkts uint8
+        [npackets, slot], lens int16 [npackets].  Returns (conn_of int32
+        [npackets], cls uint8 [npackets], accepted uint8 [max_accepted, 48]
+        (LISTEN_ACCEPT_DTYPE), n_accepted int32 [1]); accepted defaults to
+        min(npackets, max_conn) rows."""
+        npk = pkts.shape[0] if npackets is None else npackets
+        _require(0 <= npk <= 1 << 31)
+        _require(pkts.is_contiguous() and pkts.element_size() == 1 and pkts.dim() == 2 and pkts.shape[0] >= npk)
+        self._check(names, npk, 1, "names", LISTEN_NAME_BYTES)
+        self._check(lens, npk, 2, "lens")
+        dev = self._dev()
+        if conn_of is None:
+            conn_of = torch.zeros(npk, dtype=torch.int32, device=dev)
+        if cls is None:
+            cls = torch.zeros(npk, dtype=torch.uint8, device=dev)
+        if accepted is None:
+            accepted = torch.zeros((min(npk, self.max_conn), 48), dtype=torch.uint8, device=dev)
+        if n_accepted is None:
+            n_accepted = torch.zeros(1, dtype=torch.int32, device=dev)
+        self._check(conn_of, npk, 4, "conn_of")
+        self._check(cls, npk, 1, "cls")
+        self._check(accepted, accepted.shape[0], 1, "accepted", 48)
+        self._check(n_accepted, 1, 4, "n_accepted")
+        _raise(load_library().ugo_fec_listen_route(
+            self._h, names.data_ptr(), pkts.data_ptr(), pkts.shape[1], lens.data_ptr(), npk, conn_of.data_ptr(),
+            cls.data_ptr(), accepted.data_ptr() if accepted.shape[0] else None, accepted.shape[0],
+            n_accepted.data_ptr(), _stream_handle(stream)))
+        return conn_of, cls, accepted, n_accepted
+
+    def remap(self, new_index, nconn_new: int, status=None, stream=None):
+        """ugo_fec_listen_remap.  new_index int32 [nconn] (STREAM_NO_CONN as -1
+        closes a member).  Returns status int32 [1]: 0 or LISTEN_REMAP_* bits."""
+        _require(isinstance(nconn_new, int) and nconn_new >= 0)
+        self._check(new_index, new_index.shape[0], 4, "new_index")
+        _require(new_index.shape[0] <= LISTEN_MAX_CONN)
+        if status is None:
+            status = torch.zeros(1, dtype=torch.int32, device=self._dev())
+        self._check(status, 1, 4, "status")
+        _raise(load_library().ugo_fec_listen_remap(
+            self._h, new_index.data_ptr() if new_index.shape[0] else None, new_index.shape[0], nconn_new,
+            status.data_ptr(), _stream_handle(stream)))
+        return status
+
+    def names(self, conn_of, npackets: Optional[int] = None, names_out=None, name_lens=None, stream=None):
+        """ugo_fec_listen_names.  conn_of int32 [npackets] as StreamTxSet.plan
+        wrote it.  Returns (names_out uint8 [npackets, 32], name_lens int32
+        [npackets])."""
+        npk = conn_of.shape[0] if npackets is None else npackets
+        _require(0 <= npk <= 1 << 31)
+        self._check(conn_of, npk, 4, "conn_of")
+        if names_out is None:
+            names_out = torch.zeros((npk, LISTEN_NAME_BYTES), dtype=torch.uint8, device=self._dev())
+        if name_lens is None:
+            name_lens = torch.zeros(npk, dtype=torch.int32, device=self._dev())
+        self._check(names_out, npk, 1, "names_out", LISTEN_NAME_BYTES)
+        self._check(name_lens, npk, 4, "name_lens")
+        _raise(load_library().ugo_fec_listen_names(self._h, conn_of.data_ptr(), npk, names_out.data_ptr(),
+                                                   name_lens.data_ptr(), _stream_handle(stream)))
+        return names_out, name_lens
+
+    def state(self) -> np.ndarray:
+        """The table's record (LISTEN_STATE_DTYPE scalar); waits for the last call on the table."""
+        out = np.zeros(1, LISTEN_STATE_DTYPE)
+        _raise(load_library().ugo_fec_listen_state(self._h, out.ctypes.data))
+        return out[0]
+
+    def entries(self, out=None, stream=None) -> np.ndarray:
+        """ugo_fec_listen_entries, then the rows that hold an entry
+        (LISTEN_ENTRY_DTYPE), in member order; synchronises."""
+        if out is None:
+            out = torch.zeros((self.max_conn, 32), dtype=torch.uint8, device=self._dev())
+        self._check(out, out.shape[0], 1, "out", 32)
+        _raise(load_library().ugo_fec_listen_entries(self._h, out.data_ptr(), out.shape[0], _stream_handle(stream)))
+        rows = out.cpu().numpy().view(LISTEN_ENTRY_DTYPE).reshape(-1)
+        return rows[rows["member"] != STREAM_NO_CONN]
 
 
 def rc4_keystream(key: bytes, n: int) -> bytes:

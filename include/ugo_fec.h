@@ -72,7 +72,9 @@ extern "C" {
  *    UGO_FEC_KERNEL_SENT (13, defined there); congestion control,
  *    ugo_fec_cc_* (ugo_cc.h), with UGO_FEC_KERNEL_CC (14, defined there); the
  *    connection table, ugo_fec_listen_* (ugo_listen.h), with
- *    UGO_FEC_KERNEL_LISTEN (15, defined there). */
+ *    UGO_FEC_KERNEL_LISTEN (15, defined there); the connection loop,
+ *    ugo_fec_loop_* (ugo_loop.h), with UGO_FEC_KERNEL_LOOP (16, defined
+ *    there). */
 #define UGO_FEC_ABI_VERSION 9
 
 /* Status codes.  1..5 map 1:1 onto the klauspost/reedsolomon error values

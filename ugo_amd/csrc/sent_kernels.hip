@@ -51,6 +51,7 @@
 #include <cstdint>
 
 #include "launch.hpp"
+#include "sent_device.hpp"
 #include "sent_kernels.hpp"
 
 namespace ugo {
@@ -796,13 +797,7 @@ __global__ __launch_bounds__(256) void k_sent_rto(SentRtoArgs a) {
   SentRecord* rec = e.rec;
   bool due = false;
   if (!rec->err && rec->last_sent_us != 0) {
-    u64 rto = a.delay_us[c];
-    if (rto == 0) rto = UGO_SENT_RTO_DEFAULT_US;
-    if (rto > UGO_SENT_RTO_MAX_US) rto = UGO_SENT_RTO_MAX_US;
-    if (rto < UGO_SENT_RTO_MIN_US) rto = UGO_SENT_RTO_MIN_US;
-    const uint32_t sh = rec->rto_count < 16u ? rec->rto_count : 16u;
-    rto <<= sh;
-    if (rto > UGO_SENT_RTO_MAX_US) rto = UGO_SENT_RTO_MAX_US;
+    const u64 rto = sent_rto_us(a.delay_us[c], rec->rto_count);
     const u64 at = rec->last_sent_us + rto;
     due = at >= rto && a.now_us >= at;  // a deadline past 2^64 never comes
   }

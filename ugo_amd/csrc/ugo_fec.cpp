@@ -39,7 +39,9 @@
 #include "host/sent_args.hpp"
 #include "cc_kernels.hpp"
 #include "host/listen_args.hpp"
+#include "host/loop_args.hpp"
 #include "listen_kernels.hpp"
+#include "loop_kernels.hpp"
 #include "sent_kernels.hpp"
 
 namespace {
@@ -2223,6 +2225,24 @@ int ugo_fec_packet_encode(ugo_fec* c, const ugo_pkt_info* info, const uint64_t* 
   return hip_status(ugo::kern::launch_packet_encode(a, static_cast<hipStream_t>(stream)));
 }
 
+// ---------------------------------------------------------------- connection loop: the set, before the sets it reads
+// The connection loop of a set (include/ugo_loop.h): one record per member of four neighbouring sets.
+struct ugo_loop_set {
+  ugo_fec* ctx = nullptr;
+  ugo_stream_rx_set* stream_rx = nullptr;  // all four null once one of them is gone: every call is then an
+  ugo_ack_rx_set* ack_rx = nullptr;        // argument error
+  ugo_stream_tx_set* stream_tx = nullptr;
+  ugo_sent_tx_set* sent_tx = nullptr;
+  ugo::kern::LoopTables t{};   // recs, call, block_a, block_b and words are the set's own
+  hipStream_t last = nullptr;  // the stream of the last call on the set
+  bool used = false;
+};
+
+namespace {
+// A neighbouring set goes: wait for the loop sets that read its table, then they are closed.
+void loop_sets_close(const std::vector<ugo_loop_set*>& sets);
+}  // namespace
+
 // ---------------------------------------------------------------- stream delivery (include/ugo_stream.h)
 struct ugo_stream_rx {
   ugo_fec* ctx = nullptr;
@@ -2236,6 +2256,7 @@ struct ugo_stream_rx {
 
 struct ugo_stream_rx_set {
   ugo_fec* ctx = nullptr;
+  std::vector<ugo_loop_set*> loop_sets;  // the live loop sets that read its table
   std::vector<ugo_stream_rx*> members;
   ugo::kern::StreamSetEntry* table = nullptr;  // device, [nconn], uploaded once
   ugo_stream_rx_state* gathered = nullptr;     // device, [nconn], for ugo_fec_stream_set_state
@@ -2450,6 +2471,7 @@ void ugo_fec_stream_set_destroy(ugo_stream_rx_set* set) {
   {
     DeviceGuard g(set->ctx->device);
     if (set->used) (void)hipStreamSynchronize(set->last);
+    loop_sets_close(set->loop_sets);
     (void)hipFree(set->table);
     (void)hipFree(set->gathered);
   }
@@ -2533,6 +2555,7 @@ struct ugo_stream_tx {
 
 struct ugo_stream_tx_set {
   ugo_fec* ctx = nullptr;
+  std::vector<ugo_loop_set*> loop_sets;  // the live loop sets that read its table
   std::vector<ugo_stream_tx*> members;
   ugo::kern::StreamTxEntry* table = nullptr;         // device, [nconn], uploaded once
   ugo_stream_tx_state* gathered = nullptr;           // device, [nconn], for ugo_fec_stream_tx_set_state
@@ -2665,6 +2688,7 @@ void ugo_fec_stream_tx_set_destroy(ugo_stream_tx_set* set) {
   {
     DeviceGuard g(set->ctx->device);
     if (set->used) (void)hipStreamSynchronize(set->last);
+    loop_sets_close(set->loop_sets);
     (void)hipFree(set->table);
     (void)hipFree(set->gathered);
     (void)hipFree(set->scratch);
@@ -2843,6 +2867,7 @@ struct ugo_ack_rx {
 
 struct ugo_ack_rx_set {
   ugo_fec* ctx = nullptr;
+  std::vector<ugo_loop_set*> loop_sets;  // the live loop sets that read its table
   std::vector<ugo_ack_rx*> members;
   ugo::kern::AckEntry* table = nullptr;  // device, [nconn], uploaded once
   ugo_ack_state* gathered = nullptr;     // device, [nconn], for ugo_fec_ack_set_state
@@ -2972,6 +2997,7 @@ void ugo_fec_ack_set_destroy(ugo_ack_rx_set* set) {
   {
     DeviceGuard g(set->ctx->device);
     if (set->used) (void)hipStreamSynchronize(set->last);
+    loop_sets_close(set->loop_sets);
     (void)hipFree(set->table);
     (void)hipFree(set->gathered);
     (void)hipFree(set->call);
@@ -3081,6 +3107,7 @@ struct ugo_sent_tx {
 
 struct ugo_sent_tx_set {
   ugo_fec* ctx = nullptr;
+  std::vector<ugo_loop_set*> loop_sets;  // the live loop sets that read its table
   std::vector<ugo_sent_tx*> members;
   ugo::kern::SentEntry* table = nullptr;  // device, [nconn], uploaded once
   ugo_sent_state* gathered = nullptr;     // device, [nconn], for ugo_fec_sent_set_state
@@ -3252,6 +3279,7 @@ void ugo_fec_sent_set_destroy(ugo_sent_tx_set* set) {
   {
     DeviceGuard g(set->ctx->device);
     if (set->used) (void)hipStreamSynchronize(set->last);
+    loop_sets_close(set->loop_sets);
     for (ugo_cc_set* cs : set->cc_sets) {  // they read the table: wait for them, then they are closed
       if (cs->used) (void)hipStreamSynchronize(cs->last);
       cs->sent = nullptr;
@@ -3564,6 +3592,253 @@ int ugo_fec_cc_set_state(ugo_cc_set* set, ugo_cc_state* host_out) {
   if (!g.ok) return UGO_FEC_ERR_NO_DEVICE;
   if (set->used && hipStreamSynchronize(set->last) != hipSuccess) return UGO_FEC_ERR_HIP;
   return hip_status(hipMemcpy(host_out, set->recs, set->nconn * sizeof(*host_out), hipMemcpyDeviceToHost));
+}
+
+// ---------------------------------------------------------------- connection loop (include/ugo_loop.h)
+namespace {
+void loop_set_forget(std::vector<ugo_loop_set*>& sets, ugo_loop_set* set) {
+  sets.erase(std::remove(sets.begin(), sets.end(), set), sets.end());
+}
+
+// Takes the set out of its four neighbours' lists; its calls are argument errors from then on.
+void loop_set_detach(ugo_loop_set* set) {
+  if (set->stream_rx) loop_set_forget(set->stream_rx->loop_sets, set);
+  if (set->ack_rx) loop_set_forget(set->ack_rx->loop_sets, set);
+  if (set->stream_tx) loop_set_forget(set->stream_tx->loop_sets, set);
+  if (set->sent_tx) loop_set_forget(set->sent_tx->loop_sets, set);
+  set->stream_rx = nullptr;
+  set->ack_rx = nullptr;
+  set->stream_tx = nullptr;
+  set->sent_tx = nullptr;
+}
+
+void loop_sets_close(const std::vector<ugo_loop_set*>& sets) {
+  const std::vector<ugo_loop_set*> copy = sets;  // detach edits the list
+  for (ugo_loop_set* ls : copy) {
+    if (ls->used) (void)hipStreamSynchronize(ls->last);
+    loop_set_detach(ls);
+  }
+}
+
+int loop_enter(ugo_loop_set* set) {
+  if (!set || !set->sent_tx) return UGO_FEC_ERR_INVALID_ARG;
+  if (set->ctx->poisoned) return UGO_FEC_ERR_HIP;
+  return UGO_FEC_OK;
+}
+
+int loop_set_build(ugo_fec* c, ugo_stream_rx_set* srx, ugo_ack_rx_set* arx, ugo_stream_tx_set* stx,
+                   ugo_sent_tx_set* sent, const ugo_loop_params& p, uint64_t now_us, ugo_loop_set** out) {
+  DeviceGuard g(c->device);
+  if (!g.ok) return UGO_FEC_ERR_NO_DEVICE;
+  const size_t nconn = sent->members.size();
+  const std::vector<ugo_loop_state> init(nconn, ugo::loopargs::initial(now_us));
+  const std::vector<uint32_t> idle(4 * nconn, ugo::kern::kLoopIdle);
+  const unsigned long long words[2] = {0ull, ~0ull};
+  srx->loop_sets.reserve(srx->loop_sets.size() + 1);  // what may throw comes before the set exists
+  arx->loop_sets.reserve(arx->loop_sets.size() + 1);
+  stx->loop_sets.reserve(stx->loop_sets.size() + 1);
+  sent->loop_sets.reserve(sent->loop_sets.size() + 1);
+  ugo_loop_set* set = new (std::nothrow) ugo_loop_set();
+  if (!set) return UGO_FEC_ERR_HIP;
+  set->ctx = c;
+  set->stream_rx = srx;
+  set->ack_rx = arx;
+  set->stream_tx = stx;
+  set->sent_tx = sent;
+  srx->loop_sets.push_back(set);
+  arx->loop_sets.push_back(set);
+  stx->loop_sets.push_back(set);
+  sent->loop_sets.push_back(set);
+  ugo::kern::LoopTables& t = set->t;
+  t.stream_rx = srx->table;
+  t.ack_rx = arx->table;
+  t.stream_tx = stx->table;
+  t.sent_tx = sent->table;
+  t.p = p;
+  t.nconn = static_cast<uint32_t>(nconn);
+  const size_t nblock = ugo::kern::kLoopScanBlock * sizeof(uint32_t);
+  if (hipMalloc(&t.recs, nconn * sizeof(ugo_loop_state)) != hipSuccess ||
+      hipMalloc(&t.call, nconn * sizeof(ugo::kern::LoopCall)) != hipSuccess ||
+      hipMalloc(&t.block_a, nblock) != hipSuccess || hipMalloc(&t.block_b, nblock) != hipSuccess ||
+      hipMalloc(&t.words, sizeof(words)) != hipSuccess || hipMemset(t.block_a, 0, nblock) != hipSuccess ||
+      hipMemset(t.block_b, 0, nblock) != hipSuccess ||
+      hipMemcpy(t.recs, init.data(), nconn * sizeof(ugo_loop_state), hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(t.call, idle.data(), nconn * sizeof(ugo::kern::LoopCall), hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(t.words, words, sizeof(words), hipMemcpyHostToDevice) != hipSuccess ||
+      hipStreamSynchronize(nullptr) != hipSuccess) {
+    (void)hipGetLastError();
+    ugo_fec_loop_set_destroy(set);
+    return UGO_FEC_ERR_HIP;
+  }
+  *out = set;
+  return UGO_FEC_OK;
+}
+}  // namespace
+
+int ugo_fec_loop_set_create(ugo_fec* c, ugo_stream_rx_set* srx, ugo_ack_rx_set* arx, ugo_stream_tx_set* stx,
+                            ugo_sent_tx_set* sent, const ugo_loop_params* params, uint64_t now_us,
+                            ugo_loop_set** out) {
+  static_assert(sizeof(ugo_loop_state) == 64 && sizeof(ugo_loop_params) == 24, "the layouts ugo_loop.h states");
+  static_assert(UGO_FEC_KERNEL_LOOP == ugo::kern::kKLoop, "kernel class matches loop_kernels.hpp");
+  if (out) *out = nullptr;
+  if (!c || !srx || !arx || !stx || !sent || !out || srx->ctx != c || arx->ctx != c || stx->ctx != c ||
+      sent->ctx != c)
+    return UGO_FEC_ERR_INVALID_ARG;
+  if (!ugo::loopargs::nconn_ok(srx->members.size(), arx->members.size(), stx->members.size(), sent->members.size()))
+    return UGO_FEC_ERR_INVALID_ARG;
+  const ugo_loop_params p = params ? *params : ugo::loopargs::defaults();
+  if (!ugo::loopargs::params_ok(p)) return UGO_FEC_ERR_INVALID_ARG;
+  if (c->poisoned) return UGO_FEC_ERR_HIP;
+  try {
+    return loop_set_build(c, srx, arx, stx, sent, p, now_us, out);
+  } catch (const std::bad_alloc&) {  // nothing throws through the C boundary
+    return UGO_FEC_ERR_HIP;
+  }
+}
+
+void ugo_fec_loop_set_destroy(ugo_loop_set* set) {
+  if (!set) return;
+  {
+    DeviceGuard g(set->ctx->device);
+    if (set->used) (void)hipStreamSynchronize(set->last);
+    (void)hipFree(set->t.recs);
+    (void)hipFree(set->t.call);
+    (void)hipFree(set->t.block_a);
+    (void)hipFree(set->t.block_b);
+    (void)hipFree(set->t.words);
+  }
+  loop_set_detach(set);
+  delete set;
+}
+
+int ugo_fec_loop_set_receive(ugo_loop_set* set, const ugo_pkt_info* info, uint32_t* conn_of, size_t npk,
+                             uint64_t now_us, void* stream) {
+  if (const int st = loop_enter(set)) return st;
+  if (npk == 0) return UGO_FEC_OK;
+  if (!ugo::loopargs::receive_ok(info, conn_of, npk)) return UGO_FEC_ERR_INVALID_ARG;
+  ugo_fec* c = set->ctx;
+  DeviceGuard g(c->device);
+  if (!g.ok) return UGO_FEC_ERR_NO_DEVICE;
+  if (!device_view(info) || !device_view(conn_of)) return UGO_FEC_ERR_INVALID_ARG;
+  TimerScope ts(c);
+  ugo::kern::LoopReceiveArgs a{};
+  a.t = set->t;
+  a.info = info;
+  a.conn_of = conn_of;
+  a.npk = npk;
+  a.now_us = now_us;
+  set->last = static_cast<hipStream_t>(stream);
+  set->used = true;
+  return hip_status(ugo::kern::launch_loop_receive(a, set->last));
+}
+
+int ugo_fec_loop_set_close(ugo_loop_set* set, const uint8_t* how, const uint64_t* linger_us, uint64_t now_us,
+                           void* stream) {
+  if (const int st = loop_enter(set)) return st;
+  if (!ugo::loopargs::close_ok(how, linger_us)) return UGO_FEC_ERR_INVALID_ARG;
+  ugo_fec* c = set->ctx;
+  DeviceGuard g(c->device);
+  if (!g.ok) return UGO_FEC_ERR_NO_DEVICE;
+  if (!device_view(how) || !device_view(linger_us)) return UGO_FEC_ERR_INVALID_ARG;
+  TimerScope ts(c);
+  ugo::kern::LoopCloseArgs a{};
+  a.t = set->t;
+  a.how = how;
+  a.linger_us = reinterpret_cast<const unsigned long long*>(linger_us);
+  a.now_us = now_us;
+  set->last = static_cast<hipStream_t>(stream);
+  set->used = true;
+  return hip_status(ugo::kern::launch_loop_close(a, set->last));
+}
+
+int ugo_fec_loop_set_check(ugo_loop_set* set, uint64_t now_us, uint32_t* budget, uint8_t* may_ack_only,
+                           void* stream) {
+  if (const int st = loop_enter(set)) return st;
+  if (!ugo::loopargs::check_ok(budget, may_ack_only)) return UGO_FEC_ERR_INVALID_ARG;
+  ugo_fec* c = set->ctx;
+  DeviceGuard g(c->device);
+  if (!g.ok) return UGO_FEC_ERR_NO_DEVICE;
+  if (!device_view(budget) || !device_view(may_ack_only)) return UGO_FEC_ERR_INVALID_ARG;
+  TimerScope ts(c);
+  ugo::kern::LoopCheckArgs a{};
+  a.t = set->t;
+  a.budget = budget;
+  a.may_ack_only = may_ack_only;
+  a.now_us = now_us;
+  set->last = static_cast<hipStream_t>(stream);
+  set->used = true;
+  return hip_status(ugo::kern::launch_loop_check(a, set->last));
+}
+
+int ugo_fec_loop_set_append(ugo_loop_set* set, const uint64_t* total, size_t max_packets, ugo_pkt_info* info,
+                            ugo_pkt_segment* segs, size_t max_segments, uint32_t* conn_of, uint64_t* total_out,
+                            uint8_t* appended, void* stream) {
+  if (const int st = loop_enter(set)) return st;
+  if (!ugo::loopargs::append_ok(total, max_packets, info, segs, max_segments, conn_of, total_out, appended))
+    return UGO_FEC_ERR_INVALID_ARG;
+  ugo_fec* c = set->ctx;
+  DeviceGuard g(c->device);
+  if (!g.ok) return UGO_FEC_ERR_NO_DEVICE;
+  if (!device_view(total) || !device_view(info) || !device_view(segs) || !device_view(conn_of) ||
+      !device_view(total_out) || !device_view(appended))
+    return UGO_FEC_ERR_INVALID_ARG;
+  TimerScope ts(c);
+  ugo::kern::LoopAppendArgs a{};
+  a.t = set->t;
+  a.total = reinterpret_cast<const unsigned long long*>(total);
+  a.info = info;
+  a.segs = segs;
+  a.conn_of = conn_of;
+  a.total_out = reinterpret_cast<unsigned long long*>(total_out);
+  a.appended = appended;
+  a.max_packets = max_packets;
+  a.max_segments = max_segments;
+  set->last = static_cast<hipStream_t>(stream);
+  set->used = true;
+  return hip_status(ugo::kern::launch_loop_append(a, set->last));
+}
+
+int ugo_fec_loop_set_sent(ugo_loop_set* set, const uint32_t* n_packets, const uint8_t* attached,
+                          const uint64_t* delay_us, uint64_t now_us, uint64_t* deadline_us, uint32_t* exits,
+                          uint8_t* reasons, size_t max_exits, uint64_t* n_exits, uint32_t* new_index,
+                          uint64_t* nconn_new, void* stream) {
+  if (const int st = loop_enter(set)) return st;
+  if (!ugo::loopargs::sent_ok(n_packets, attached, delay_us, deadline_us, exits, reasons, max_exits, n_exits,
+                              new_index, nconn_new))
+    return UGO_FEC_ERR_INVALID_ARG;
+  ugo_fec* c = set->ctx;
+  DeviceGuard g(c->device);
+  if (!g.ok) return UGO_FEC_ERR_NO_DEVICE;
+  if (!device_view(n_packets) || !device_view(attached) || !device_view(delay_us) || !device_view(deadline_us) ||
+      !device_view(exits) || !device_view(reasons) || !device_view(n_exits) || !device_view(new_index) ||
+      !device_view(nconn_new))
+    return UGO_FEC_ERR_INVALID_ARG;
+  TimerScope ts(c);
+  ugo::kern::LoopSentArgs a{};
+  a.t = set->t;
+  a.n_packets = n_packets;
+  a.attached = attached;
+  a.delay_us = reinterpret_cast<const unsigned long long*>(delay_us);
+  a.deadline_us = reinterpret_cast<unsigned long long*>(deadline_us);
+  a.exits = exits;
+  a.reasons = reasons;
+  a.n_exits = reinterpret_cast<unsigned long long*>(n_exits);
+  a.new_index = new_index;
+  a.nconn_new = reinterpret_cast<unsigned long long*>(nconn_new);
+  a.max_exits = max_exits;
+  a.now_us = now_us;
+  set->last = static_cast<hipStream_t>(stream);
+  set->used = true;
+  return hip_status(ugo::kern::launch_loop_sent(a, set->last));
+}
+
+int ugo_fec_loop_set_state(ugo_loop_set* set, ugo_loop_state* host_out) {
+  if (!set || !host_out) return UGO_FEC_ERR_INVALID_ARG;
+  DeviceGuard g(set->ctx->device);
+  if (!g.ok) return UGO_FEC_ERR_NO_DEVICE;
+  if (set->used && hipStreamSynchronize(set->last) != hipSuccess) return UGO_FEC_ERR_HIP;
+  return hip_status(
+      hipMemcpy(host_out, set->t.recs, set->t.nconn * sizeof(*host_out), hipMemcpyDeviceToHost));
 }
 
 // ---------------------------------------------------------------- connection table (include/ugo_listen.h)

@@ -47,6 +47,7 @@ ACK_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ugo_ack.h")
 SENT_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ugo_sent.h")
 CC_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ugo_cc.h")
 LISTEN_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ugo_listen.h")
+LOOP_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ugo_loop.h")
 
 OK = 0
 RECONSTRUCT_DATA_ONLY = 1
@@ -111,7 +112,7 @@ PKT_INFO_DTYPE = np.dtype([("packet_number", "<u8"), ("stop_waiting", "<u8"), ("
 # include/ugo_fec.h launch timing
 KERNEL_NAMES = {1: "encode", 2: "reconstruct", 3: "prepare", 4: "bytes", 5: "rx_assemble", 6: "tx_assemble",
                 7: "packet_decode", 8: "packet_encode", 9: "stream_deliver", 10: "stream_read", 11: "stream_tx",
-                12: "ack", 13: "sent", 14: "cc", 15: "listen"}
+                12: "ack", 13: "sent", 14: "cc", 15: "listen", 16: "loop"}
 KERNEL_IDS = {v: k for k, v in KERNEL_NAMES.items()}
 LAUNCH_TIME_DTYPE = np.dtype([("kernel", "<u4"), ("ms", "<f4")])
 PKT_SEGMENT_DTYPE = np.dtype([("offset", "<u8"), ("data_off", "<u4"), ("len", "<u2"), ("avail", "<u2")])
@@ -213,6 +214,19 @@ LISTEN_ENTRY_DTYPE = np.dtype([("ip", "u1", (16,)), ("scope", "<u4"), ("port", "
                                ("reserved", "<u4")])
 assert (LISTEN_ACCEPT_DTYPE.itemsize == 48 and LISTEN_STATE_DTYPE.itemsize == 80 and
         LISTEN_ENTRY_DTYPE.itemsize == 32)
+# include/ugo_loop.h, the connection loop
+LOOP_DEFAULTS = dict(ack_delay_us=5000, idle_us=300000000, max_retries=10)
+LOOP_PEER_ACK_FIN, LOOP_PEER_RST, LOOP_BAD_PACKET, LOOP_CLOSED, LOOP_FAILURES, LOOP_SENT_ERR = 1, 2, 3, 4, 5, 6
+LOOP_ACK_ERR, LOOP_STREAM_ERR, LOOP_IDLE, LOOP_LINGER, LOOP_ABORT = 7, 8, 9, 10, 11
+LOOP_PENDING_NONE, LOOP_PENDING_FIN, LOOP_PENDING_RST = 0, 1, 2
+LOOP_HOW_CLOSE, LOOP_HOW_ABORT, LOOP_HOW_NODELAY_ON, LOOP_HOW_NODELAY_OFF = 1, 2, 4, 8
+LOOP_PARAMS_DTYPE = np.dtype([("ack_delay_us", "<u8"), ("idle_us", "<u8"), ("max_retries", "<u4"),
+                              ("reserved", "<u4")])
+LOOP_STATE_DTYPE = np.dtype([("last_activity_us", "<u8"), ("origin_ack_us", "<u8"), ("linger_deadline_us", "<u8"),
+                             ("exit_us", "<u8"), ("dropped", "<u8"), ("closed", "u1"), ("fin_sent", "u1"),
+                             ("fin_rcvd", "u1"), ("ack_no_delay", "u1"), ("exited", "u1"), ("reason", "u1"),
+                             ("pending", "u1"), ("reported", "u1"), ("reserved", "u1", (16,))])
+assert LOOP_PARAMS_DTYPE.itemsize == 24 and LOOP_STATE_DTYPE.itemsize == 64
 
 
 def load_library(path: str = LIB_PATH):
@@ -323,6 +337,15 @@ def load_library(path: str = LIB_PATH):
     lib.ugo_fec_listen_remap.argtypes = [vp, vp, sz, sz, vp, vp]
     lib.ugo_fec_listen_names.argtypes = [vp, vp, sz, vp, vp, vp]
     lib.ugo_fec_listen_entries.argtypes = [vp, vp, sz, vp]
+    lib.ugo_fec_loop_set_create.argtypes = [vp, vp, vp, vp, vp, vp, u64, ctypes.POINTER(vp)]
+    lib.ugo_fec_loop_set_destroy.argtypes = [vp]
+    lib.ugo_fec_loop_set_destroy.restype = None
+    lib.ugo_fec_loop_set_receive.argtypes = [vp, vp, vp, sz, u64, vp]
+    lib.ugo_fec_loop_set_close.argtypes = [vp, vp, vp, u64, vp]
+    lib.ugo_fec_loop_set_check.argtypes = [vp, u64, vp, vp, vp]
+    lib.ugo_fec_loop_set_append.argtypes = [vp, vp, sz, vp, vp, sz, vp, vp, vp, vp]
+    lib.ugo_fec_loop_set_sent.argtypes = [vp, vp, vp, vp, u64, vp, vp, vp, sz, vp, vp, vp, vp]
+    lib.ugo_fec_loop_set_state.argtypes = [vp, vp]
     lib.ugo_fec_reconstruct_rows.argtypes = [vp, vp, vp, sz, sz, vp, sz, sz, u, vp, vp]
     lib.ugo_fec_lossy_groups.argtypes = [vp, vp, sz, u, vp, vp, vp]
     lib.ugo_fec_rx_recover_host.argtypes = [vp, vp, sz, vp, sz, vp, ctypes.c_uint64, sz, sz, vp, vp, vp, sz, sz, vp,
@@ -340,9 +363,10 @@ def load_library(path: str = LIB_PATH):
 
 
 def header_symbols(paths=(HEADER_PATH, CONN_HEADER_PATH, PKT_HEADER_PATH, STREAM_HEADER_PATH,
-                          ACK_HEADER_PATH, SENT_HEADER_PATH, CC_HEADER_PATH, LISTEN_HEADER_PATH)) -> List[str]:
+                          ACK_HEADER_PATH, SENT_HEADER_PATH, CC_HEADER_PATH, LISTEN_HEADER_PATH,
+                          LOOP_HEADER_PATH)) -> List[str]:
     """Every entry point declared in include/ugo_fec.h, ugo_fec_conn.h, ugo_pkt.h, ugo_stream.h, ugo_ack.h,
-    ugo_sent.h, ugo_cc.h and ugo_listen.h."""
+    ugo_sent.h, ugo_cc.h, ugo_listen.h and ugo_loop.h."""
     out = set()
     for path in paths:
         src = open(path).read()
@@ -1868,6 +1892,169 @@ class ListenTable:
         _raise(load_library().ugo_fec_listen_entries(self._h, out.data_ptr(), out.shape[0], _stream_handle(stream)))
         rows = out.cpu().numpy().view(LISTEN_ENTRY_DTYPE).reshape(-1)
         return rows[rows["member"] != STREAM_NO_CONN]
+
+
+class LoopSet:
+    """The connection loop of a set of connections (include/ugo_loop.h): the
+    timers, FIN / RST and the exits, one record per member of a StreamRxSet, an
+    AckRxSet, a StreamTxSet and a SentTxSet of the same size.  Per batch:
+    receive after packet_decode, check before StreamTxSet.plan, append after it,
+    sent after StreamTxSet.encode; close between batches.  Operands are tensors
+    in device or pinned host memory; nothing is synchronised but states().
+    Close it before the four sets."""
+
+    def __init__(self, enc: Encoder, stream_rx: "StreamRxSet", ack_rx: "AckRxSet", stream_tx: "StreamTxSet",
+                 sent_tx: "SentTxSet", now_us: int = 0, **params):
+        p = self.check_params(**params)
+        sets = (stream_rx, ack_rx, stream_tx, sent_tx)
+        kinds = (StreamRxSet, AckRxSet, StreamTxSet, SentTxSet)
+        _require(all(isinstance(s, k) and getattr(s, "_h", None) and s._enc is enc for s, k in zip(sets, kinds)),
+                 "the four sets must be open sets of the same context")
+        _require(len({s.nconn for s in sets}) == 1, "the four sets must have the same number of members")
+        _require(0 <= now_us < 1 << 64)
+        arr = np.array([(p["ack_delay_us"], p["idle_us"], p["max_retries"], 0)], LOOP_PARAMS_DTYPE)
+        h = ctypes.c_void_p()
+        _raise(load_library().ugo_fec_loop_set_create(enc._h, stream_rx._h, ack_rx._h, stream_tx._h, sent_tx._h,
+                                                      arr.ctypes.data if params else None, now_us, ctypes.byref(h)))
+        self._h, self._enc, self.sets = h, enc, sets  # the context and the four sets must outlive the set
+        self.nconn, self.params, self.device = sent_tx.nconn, p, enc.device
+
+    @staticmethod
+    def check_params(**params):
+        _require(set(params) <= set(LOOP_DEFAULTS), f"parameters are {sorted(LOOP_DEFAULTS)}")
+        p = dict(LOOP_DEFAULTS, **params)
+        _require(all(isinstance(v, int) for v in p.values()))
+        _require(0 <= p["ack_delay_us"] < 1 << 64 and 1 <= p["idle_us"] < 1 << 64 and
+                 0 <= p["max_retries"] < 1 << 32, "idle_us must be at least 1")
+        return p
+
+    def close(self):
+        if getattr(self, "_h", None):
+            load_library().ugo_fec_loop_set_destroy(self._h)
+            self._h = None
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _dev(self):
+        return torch.device("cuda", self.device)
+
+    def _per_conn(self, t, item: int, name: str):
+        _require(t.is_contiguous() and t.element_size() == item and tuple(t.shape) == (self.nconn,),
+                 f"{name} must be contiguous, {item}-byte, [nconn]")
+
+    @staticmethod
+    def _list(t, n: int, item: int, name: str, row=None):
+        shape = (n,) if row is None else (n, row)
+        _require(t.is_contiguous() and t.element_size() == item and t.dim() == len(shape) and t.shape[0] >= n and
+                 tuple(t.shape[1:]) == shape[1:], f"{name} must be contiguous, {item}-byte, at least {shape}")
+
+    def receive(self, info, conn_of, now_us: int, npackets: Optional[int] = None, stream=None):
+        """ugo_fec_loop_set_receive: info uint8 [npackets, 64] as packet_decode
+        wrote it, conn_of int32 [npackets], masked in place.  Returns conn_of."""
+        npk = info.shape[0] if npackets is None else npackets
+        _require(0 <= npk <= 1 << 31 and 0 <= now_us < 1 << 64)
+        self._list(info, npk, 1, "info", 64)
+        self._list(conn_of, npk, 4, "conn_of")
+        _raise(load_library().ugo_fec_loop_set_receive(self._h, info.data_ptr() if npk else None,
+                                                       conn_of.data_ptr() if npk else None, npk, now_us,
+                                                       _stream_handle(stream)))
+        return conn_of
+
+    def close_members(self, how, now_us: int, linger_us=None, stream=None):
+        """ugo_fec_loop_set_close: how uint8 [nconn] of LOOP_HOW_* bits,
+        linger_us int64 [nconn] or None."""
+        _require(0 <= now_us < 1 << 64)
+        self._per_conn(how, 1, "how")
+        if linger_us is not None:
+            self._per_conn(linger_us, 8, "linger_us")
+        _raise(load_library().ugo_fec_loop_set_close(self._h, how.data_ptr(),
+                                                     None if linger_us is None else linger_us.data_ptr(), now_us,
+                                                     _stream_handle(stream)))
+
+    def check(self, now_us: int, budget, may_ack_only=None, stream=None):
+        """ugo_fec_loop_set_check: budget int32 [nconn], zeroed in place where a
+        member may send no data.  Returns may_ack_only uint8 [nconn]: the input
+        of AckRxSet.attach."""
+        _require(0 <= now_us < 1 << 64)
+        self._per_conn(budget, 4, "budget")
+        if may_ack_only is None:
+            may_ack_only = torch.zeros(self.nconn, dtype=torch.uint8, device=self._dev())
+        self._per_conn(may_ack_only, 1, "may_ack_only")
+        _raise(load_library().ugo_fec_loop_set_check(self._h, now_us, budget.data_ptr(), may_ack_only.data_ptr(),
+                                                     _stream_handle(stream)))
+        return may_ack_only
+
+    def append(self, total, info, segs, conn_of, total_out=None, appended=None, max_packets: Optional[int] = None,
+               stream=None):
+        """ugo_fec_loop_set_append: total int64 [1], info uint8 [max_packets, 64],
+        segs uint8 [max_packets, max_segments, 16], conn_of int32 [max_packets] as
+        StreamTxSet.plan wrote them.  Returns (total_out int64 [1], appended uint8
+        [nconn]); total_out defaults to total itself."""
+        cap = info.shape[0] if max_packets is None else max_packets
+        _require(0 <= cap <= 1 << 31)
+        self._list(total, 1, 8, "total")
+        self._list(info, cap, 1, "info", 64)
+        _require(segs.is_contiguous() and segs.element_size() == 1 and segs.dim() == 3 and segs.shape[0] >= cap and
+                 1 <= segs.shape[1] <= 0xffff and segs.shape[2] == 16, "segs must be uint8 [max_packets, S, 16]")
+        self._list(conn_of, cap, 4, "conn_of")
+        if total_out is None:
+            total_out = total
+        if appended is None:
+            appended = torch.zeros(self.nconn, dtype=torch.uint8, device=self._dev())
+        self._list(total_out, 1, 8, "total_out")
+        self._per_conn(appended, 1, "appended")
+        _raise(load_library().ugo_fec_loop_set_append(self._h, total.data_ptr(), cap, info.data_ptr(),
+                                                      segs.data_ptr(), segs.shape[1], conn_of.data_ptr(),
+                                                      total_out.data_ptr(), appended.data_ptr(),
+                                                      _stream_handle(stream)))
+        return total_out, appended
+
+    def sent(self, n_packets, attached, now_us: int, delay_us=None, max_exits: Optional[int] = None, remap=False,
+             out=None, stream=None):
+        """ugo_fec_loop_set_sent: n_packets int32 [nconn] as StreamTxSet.plan
+        wrote it, attached uint8 [nconn] as AckRxSet.attach wrote it, delay_us
+        int64 [nconn] as CcSet.ack wrote it or None.  Returns (deadline_us int64
+        [1], exits int32 [max_exits], reasons uint8 [max_exits], n_exits int64 [1],
+        new_index int32 [nconn] or None, nconn_new int64 [1] or None); out: the
+        same tuple, preallocated.  max_exits defaults to nconn."""
+        _require(0 <= now_us < 1 << 64)
+        self._per_conn(n_packets, 4, "n_packets")
+        self._per_conn(attached, 1, "attached")
+        if delay_us is not None:
+            self._per_conn(delay_us, 8, "delay_us")
+        dev = self._dev()
+        if out is None:
+            cap = self.nconn if max_exits is None else max_exits
+            out = (torch.zeros(1, dtype=torch.int64, device=dev), torch.zeros(cap, dtype=torch.int32, device=dev),
+                   torch.zeros(cap, dtype=torch.uint8, device=dev), torch.zeros(1, dtype=torch.int64, device=dev),
+                   torch.zeros(self.nconn, dtype=torch.int32, device=dev) if remap else None,
+                   torch.zeros(1, dtype=torch.int64, device=dev) if remap else None)
+        deadline, exits, reasons, n_exits, new_index, nconn_new = out
+        cap = exits.shape[0] if max_exits is None else max_exits
+        self._list(deadline, 1, 8, "deadline_us")
+        self._list(exits, cap, 4, "exits")
+        self._list(reasons, cap, 1, "reasons")
+        self._list(n_exits, 1, 8, "n_exits")
+        _require((new_index is None) == (nconn_new is None), "new_index and nconn_new go together")
+        if new_index is not None:
+            self._per_conn(new_index, 4, "new_index")
+            self._list(nconn_new, 1, 8, "nconn_new")
+        _raise(load_library().ugo_fec_loop_set_sent(
+            self._h, n_packets.data_ptr(), attached.data_ptr(), None if delay_us is None else delay_us.data_ptr(),
+            now_us, deadline.data_ptr(), exits.data_ptr() if cap else None, reasons.data_ptr() if cap else None, cap,
+            n_exits.data_ptr(), None if new_index is None else new_index.data_ptr(),
+            None if nconn_new is None else nconn_new.data_ptr(), _stream_handle(stream)))
+        return out
+
+    def states(self) -> np.ndarray:
+        """The members' records (LOOP_STATE_DTYPE [nconn]); waits for the last call on the set."""
+        out = np.zeros(self.nconn, LOOP_STATE_DTYPE)
+        _raise(load_library().ugo_fec_loop_set_state(self._h, out.ctypes.data))
+        return out
 
 
 def rc4_keystream(key: bytes, n: int) -> bytes:

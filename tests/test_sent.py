@@ -262,6 +262,100 @@ def test_argument_errors_that_need_no_launch():
         fec.SentTxSet.check_members(None, [])
 
 
+# ---------------------------------------------------------------- CPU: undrained runs and truncated SACKs
+from sent_ref_b import GoSenderB  # noqa: E402
+
+
+def run_family_b(seed, p_drain, p_rto, shuffle, make_go=GoSenderB, max_ranges=None, truncated=None):
+    """run_family's loop with three changes: the drain after a call happens with
+    probability p_drain, an RTO with probability p_rto, and the reference is
+    make_go().  With max_ranges the peer's SACK is RuleAck.sack(max_ranges), and
+    truncated[0] counts the truncated ones.  Compares view() after every call,
+    the drained numbers at every drain and whether the RTO fired.  Returns
+    (compared states, states that differ)."""
+    rng = random.Random(seed)
+    loss = rng.uniform(0.0, 0.2)
+    go, rule, peer = make_go(), sr.RuleSent(1024, 1), ar.RuleAck(1024)
+    nxt, w, now = 1, 0, 1000
+    compared = differ = 0
+
+    def sack(w):
+        if max_ranges is None:
+            return _sack(peer, w)
+        la, _, rows, how = peer.sack(max_ranges)
+        truncated[0] += how == ar.TRUNCATED
+        return Ack(la, peer.lio, rows, w, 0)
+
+    for _ in range(rng.randint(4, 30)):
+        burst = list(range(nxt, nxt + rng.randint(1, 12)))
+        nxt = burst[-1] + 1
+        now += 1000
+        sw = rule.attach(True)[1]
+        go.GetStopWaitingFrame()
+        for n in burst:
+            go.sentPacket(sr._GoPacket(n, 100), now)
+        rule.record([(n, 100, 0, 0, [(10 * n, 10)]) for n in burst], now)
+        acks = []
+        for k, n in enumerate(burst):
+            if rng.random() >= loss:
+                peer.receive([(n, sw if k == 0 else 0)])
+                if rng.random() < 0.6:
+                    w += 1
+                    acks.append(sack(w))
+        while acks:
+            k = rng.randint(1, 4)
+            call, acks = acks[:k], acks[k:]
+            now += 10
+            if shuffle:
+                rng.shuffle(call)
+            rule.ack(call, now)
+            for a in (sorted(call, key=lambda a: a.la) if shuffle else call):
+                go.receivedAck(a, a.w)
+            bad = False
+            if rng.random() < p_rto:
+                now += 600_000
+                fired = rule.rto(0, now)
+                bad |= bool(go.checkRTO(0, now)) != bool(fired)
+            if rng.random() < p_drain:
+                bad |= go.drain_all() != rule.drain()[0]
+            compared += 1
+            differ += bad or go.view() != rule.view()
+    return compared, differ
+
+
+UNDRAINED = [(p, q, sh) for p in (1, 0.5, 0.1, 0) for q in (0.1, 0) for sh in (False, True)]
+
+
+@pytest.mark.parametrize("p_drain,p_rto,shuffle", UNDRAINED)
+def test_undrained_families_equal_the_reference_with_deviation_b(p_drain, p_rto, shuffle):
+    """Queued packets stay under lio for later ACKs.  The rule equals the
+    reference that carries deviation (b) and nothing else, in every state; the
+    plain reference differs wherever a drain is left out, so the comparison is
+    not empty."""
+    total = bad = plain = 0
+    for seed in range(300):
+        c, d = run_family_b(30_000 + seed, p_drain, p_rto, shuffle)
+        total, bad = total + c, bad + d
+        if p_drain < 1:
+            plain += run_family_b(30_000 + seed, p_drain, p_rto, shuffle, make_go=sr.GoSender)[1] > 0
+    assert total > 5000 and bad == 0, (total, bad)
+    assert p_drain == 1 or plain > 0, plain
+
+
+@pytest.mark.parametrize("max_ranges,p_drain", [(3, 1), (3, 0), (2, 0)])
+@pytest.mark.parametrize("p_rto", [0.1, 0])
+@pytest.mark.parametrize("shuffle", [False, True])
+def test_truncated_sacks_equal_the_reference_with_deviation_b(max_ranges, p_drain, p_rto, shuffle):
+    """The same family with the peer's SACK cut to max_ranges rows by
+    RuleAck.sack: deviation (h) against a truncated SACK."""
+    total = bad = 0
+    truncated = [0]
+    for seed in range(300):
+        c, d = run_family_b(30_000 + seed, p_drain, p_rto, shuffle, max_ranges=max_ranges, truncated=truncated)
+        total, bad = total + c, bad + d
+    assert truncated[0] > 0 and total > 5000 and bad == 0, (truncated[0], total, bad)
+
+
 # ---------------------------------------------------------------- GPU
 import torch  # noqa: E402
 

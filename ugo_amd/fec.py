@@ -362,9 +362,11 @@ def load_library(path: str = LIB_PATH):
     return lib
 
 
-def header_symbols(paths=(HEADER_PATH, CONN_HEADER_PATH, PKT_HEADER_PATH, STREAM_HEADER_PATH,
-                          ACK_HEADER_PATH, SENT_HEADER_PATH, CC_HEADER_PATH, LISTEN_HEADER_PATH,
-                          LOOP_HEADER_PATH)) -> List[str]:
+HEADER_PATHS = (HEADER_PATH, CONN_HEADER_PATH, PKT_HEADER_PATH, STREAM_HEADER_PATH, ACK_HEADER_PATH,
+                SENT_HEADER_PATH, CC_HEADER_PATH, LISTEN_HEADER_PATH, LOOP_HEADER_PATH)
+
+
+def header_symbols(paths=HEADER_PATHS) -> List[str]:
     """Every entry point declared in include/ugo_fec.h, ugo_fec_conn.h, ugo_pkt.h, ugo_stream.h, ugo_ack.h,
     ugo_sent.h, ugo_cc.h, ugo_listen.h and ugo_loop.h."""
     out = set()
@@ -372,6 +374,17 @@ def header_symbols(paths=(HEADER_PATH, CONN_HEADER_PATH, PKT_HEADER_PATH, STREAM
         src = open(path).read()
         src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
         out |= set(re.findall(r"\b(ugo_fec(?:conn)?_[a-z0-9_]+)\s*\(", src))
+    return sorted(out)
+
+
+def header_stream_symbols(paths=HEADER_PATHS) -> List[str]:
+    """The entry points of header_symbols() whose prototype ends in `void* stream`: the stream-ordered calls."""
+    out = set()
+    for path in paths:
+        src = re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
+        for name, params in re.findall(r"\b(ugo_fec(?:conn)?_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", src):
+            if re.search(r"\bvoid\s*\*\s*stream\s*$", params):
+                out.add(name)
     return sorted(out)
 
 

@@ -240,17 +240,23 @@ def write_sack(largest, in_order, ranges, delay_us) -> bytes:
         num_ranges = _num_writable_nack_ranges(ranges)
         assert num_ranges <= 0xFF
         b.append((num_ranges - 1) & 0xFF)
-        first_len = largest - ranges[0][0] + 1
+        first_len = (largest - ranges[0][0] + 1) & M64
         written += 1
     else:
-        first_len = largest - in_order + 1
+        first_len = (largest - in_order + 1) & M64
     b += put_uvarint(first_len)
     for i in range(1, len(ranges)):
-        length = ranges[i][1] - ranges[i][0] + 1
-        gap = ranges[i - 1][0] - ranges[i][1] - 1
+        length = (ranges[i][1] - ranges[i][0] + 1) & M64
+        gap = (ranges[i - 1][0] - ranges[i][1] - 1) & M64
         num = gap // 0xFF + 1
         if gap % 0xFF == 0:
             num -= 1
+        if num > num_ranges - written:
+            # ugo/packet.go:420-427: the writer emits all num blocks of a range before it
+            # looks at numRanges, so a range with more blocks than remain leaves
+            # numRangesWritten above numRanges whatever follows; stated here without
+            # the loop, whose length is the gap's (up to 2^64 / 255 blocks)
+            raise EncodeError("inconsistent number of ACK ranges written")
         if num == 1:
             b.append(gap & 0xFF)
             b += put_uvarint(length)

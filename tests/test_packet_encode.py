@@ -17,39 +17,9 @@ import pytest
 import torch
 
 import packet_ref as pr
+from packet_encode_vectors import (KEY, M64, SENTINEL, _data, _describe, _many_ranges, _pkt, _ref_encode, _round_trips,
+                                   _two_ranges)
 from ugo_amd import fec
-
-KEY = b"1234567890123456"  # ugo/listener.go:92, ugo/dial.go:132
-SENTINEL = 0xA5
-M64 = (1 << 64) - 1
-
-
-def _pkt(flags=0, sack=None, pn=1, sw=0, segments=()):
-    """sack = (largest, in_order, ranges, delay_us) or None; segments = [(offset, data)]."""
-    return {"flags": flags, "sack": sack, "pn": pn, "sw": sw, "segments": list(segments)}
-
-
-def _ref_encode(p):
-    """(status, bytes) of ugoPacket.encode: the oracle behind the reference's
-    two consistency checks (packet.go:367-372)."""
-    s = p["sack"]
-    if s is not None and s[2]:
-        if s[2][0][1] != s[0]:
-            return fec.PKT_INCONSISTENT_LARGEST_ACKED, b""
-        if s[1] != s[2][-1][0]:
-            return fec.PKT_INCONSISTENT_LOWEST_ACKED, b""
-    try:
-        return 0, pr.encode(flags=p["flags"], sack=s, packet_number=p["pn"], stop_waiting=p["sw"],
-                            segments=p["segments"])
-    except pr.EncodeError:
-        return fec.PKT_INCONSISTENT_RANGE_COUNT, b""
-
-
-def _two_ranges(gap, hi=1 << 20):
-    """A SACK of two ranges with `gap` missing packets between them."""
-    lo_last = hi - 10 - gap - 1
-    ranges = [(hi - 10, hi), (lo_last - 4, lo_last)]
-    return (hi, ranges[-1][0], ranges, 7)
 
 
 # ------------------------------------------------------------------ CPU tests
@@ -82,14 +52,6 @@ def test_oracle_long_gap_pins():
         assert _ref_encode(_pkt(sack=_two_ranges(gap)))[0] == 0
 
 
-def _many_ranges(n, hi=1 << 20):
-    ranges = []
-    for _ in range(n):  # length 3, gap 3
-        ranges.append((hi - 2, hi))
-        hi -= 6
-    return (ranges[0][1], ranges[-1][0], ranges, 0)
-
-
 def test_oracle_truncation_gap0_and_single_range_pins():
     s = _many_ranges(300)
     st, raw = _ref_encode(_pkt(sack=s, pn=1))
@@ -103,36 +65,6 @@ def test_oracle_truncation_gap0_and_single_range_pins():
 
 
 # ------------------------------------------------------------ GPU batch tools
-def _describe(pkts, rng, max_ranges, max_segments, residues=None):
-    """The encoder's input for `pkts`: info / ranges / segs arrays and one flat
-    payload buffer holding every segment's bytes at a random (or the given)
-    residue mod 16, with unrelated bytes around them."""
-    n = len(pkts)
-    info = np.zeros(n, fec.PKT_INFO_DTYPE)
-    ranges = np.zeros((n, max_ranges, 2), np.uint64)
-    segs = np.zeros((n, max_segments), fec.PKT_SEGMENT_DTYPE)
-    blob = bytearray(rng.integers(0, 256, 16, dtype=np.uint8).tobytes())
-    for i, p in enumerate(pkts):
-        I = info[i]
-        I["flags"] = p["flags"] | (0x80 if p["sack"] is not None else 0)
-        I["packet_number"], I["stop_waiting"] = p["pn"], p["sw"]
-        I["status"], I["payload_off"], I["fec_flag_lo"] = 0xDEAD, 0xBEEF, 0x5A  # ignored by the encoder
-        if p["sack"] is not None:
-            I["largest_acked"], I["largest_in_order"], rg, I["delay_us"] = p["sack"]
-            I["n_ranges"] = len(rg)
-            for k, (f, l) in enumerate(rg[:max_ranges]):
-                ranges[i, k] = (f & M64, l & M64)
-        I["n_segments"] = len(p["segments"])
-        for j, (off, data) in enumerate(p["segments"][:max_segments]):
-            want = int(rng.integers(0, 16)) if residues is None else residues[i]
-            blob += bytes((want - len(blob)) % 16)
-            segs[i, j] = (off, len(blob), len(data), 0xFFFF)  # avail is ignored
-            blob += data
-            blob += rng.integers(0, 256, int(rng.integers(0, 5)), dtype=np.uint8).tobytes()
-    blob += bytes(16)
-    return info, ranges, segs, np.frombuffer(bytes(blob), np.uint8)
-
-
 def _encode(enc, info, ranges, segs, payload, slot, payload_stride=0, framed=False, pad=None):
     """Runs the encoder over sentinel-filled slots (one guard slot behind the
     last) and checks that nothing outside [0, round_up(len, 16)) was written."""
@@ -202,10 +134,6 @@ def _random_desc(rng):
     pn = int(rng.integers(1, 1 << int(rng.integers(1, 62))))
     flags = int(rng.choice([0, pr.finFlag, pr.rstFlag])) if rng.random() < 0.2 else 0
     return _pkt(flags, sack, pn, stop, segs)
-
-
-def _data(rng, n):
-    return rng.integers(0, 256, n, dtype=np.uint8).tobytes()
 
 
 def _corpus(seed, n=600):
@@ -342,16 +270,6 @@ def test_packet_encode_rc4_pad(gpu):
         enc._h, d[0].data_ptr(), None, 0, None, 0, None, 0, 1, pad.data_ptr(), fec.PKT_FEC_FRAMED, d[1].data_ptr(),
         64, d[2].data_ptr(), d[3].data_ptr(), None)
     assert code == fec.ErrInvalidArg.code
-
-
-def _round_trips(p, st):
-    """Where decode(encode(x)) == x in the reference: encodes, no gap that is
-    a multiple of 255 (written lossily, test_packet_codec.py), not a single range."""
-    if st != 0:
-        return False
-    rg = p["sack"][2] if p["sack"] else []
-    gaps = [rg[i - 1][0] - rg[i][1] - 1 for i in range(1, len(rg))]
-    return len(rg) != 1 and not any(g >= 255 and g % 255 == 0 for g in gaps)
 
 
 @pytest.mark.gpu

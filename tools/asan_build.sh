@@ -17,7 +17,10 @@ for f in ugo_amd/csrc/fec_kernels.hip ugo_amd/csrc/rx_kernels.hip ugo_amd/csrc/t
   /opt/rocm/bin/hipcc $FLAGS $SAN -c "$f" -o "$o" &
   objs+=("$o")
 done
-for f in ugo_amd/csrc/ugo_fec.cpp ugo_amd/csrc/host/reedsolomon.cpp ugo_amd/csrc/host/fec.cpp \
+for f in ugo_amd/csrc/ugo_fec.cpp ugo_amd/csrc/ugo_fec_host.cpp ugo_amd/csrc/ugo_pkt.cpp \
+         ugo_amd/csrc/ugo_stream_rx.cpp ugo_amd/csrc/ugo_stream_tx.cpp ugo_amd/csrc/ugo_ack.cpp \
+         ugo_amd/csrc/ugo_sent.cpp ugo_amd/csrc/ugo_cc.cpp ugo_amd/csrc/ugo_loop.cpp ugo_amd/csrc/ugo_listen.cpp \
+         ugo_amd/csrc/host/reedsolomon.cpp ugo_amd/csrc/host/fec.cpp \
          ugo_amd/csrc/host/conn_abi.cpp tools/asan_driver.cpp; do
   o=$OUT/$(basename "$f" .cpp).o
   /opt/rocm/bin/hipcc -O1 -g -std=c++17 -fPIC $SAN -c "$f" -o "$o" &

@@ -1,4 +1,4 @@
-// fec_kernels.hpp -- internal interface between the C-ABI (ugo_fec.cpp) and
+// fec_kernels.hpp -- internal interface between the C-ABI (ugo_fec*.cpp) and
 // the gfx950 kernels (fec_kernels.hip).  Not part of the public ABI.
 #pragma once
 #include <hip/hip_runtime_api.h>

@@ -1,14 +1,14 @@
 // ack_args.hpp -- the host half of the receive histories (include/ugo_ack.h)
 // that needs no device: the argument rules of every ugo_fec_ack_* entry point
-// and the build of a set's member table.  Kept apart from ugo_fec.cpp so that
+// and the build of a set's member table.  Kept apart from ugo_ack.cpp so that
 // a stand-alone program can run it under a sanitizer (tools/ack_args_check.cpp).
 #pragma once
-#include <algorithm>
 #include <cstddef>
 #include <cstdint>
 #include <vector>
 
 #include "../ack_kernels.hpp"
+#include "member_list.hpp"
 
 namespace ugo {
 namespace ackargs {
@@ -30,12 +30,11 @@ struct Member {
 
 // The rules of ugo_fec_ack_set_create; members[i] null for a NULL handle.
 inline bool members_ok(const void* ctx, const Member* const* members, size_t nconn) {
-  if (!ctx || !members || nconn == 0 || nconn > kern::kAckSetMaxConn) return false;
+  // (a history listed twice would be advanced twice)
+  if (nconn > kern::kAckSetMaxConn || !ugo::members::list_ok(ctx, members, nconn)) return false;
   for (size_t i = 0; i < nconn; ++i)
-    if (!members[i] || members[i]->ctx != ctx || !window_ok(members[i]->window_packets)) return false;
-  std::vector<const Member*> sorted(members, members + nconn);  // a history listed twice would be advanced twice
-  std::sort(sorted.begin(), sorted.end());
-  return std::adjacent_find(sorted.begin(), sorted.end()) == sorted.end();
+    if (!window_ok(members[i]->window_packets)) return false;
+  return true;
 }
 
 // One table entry per member, in set order.

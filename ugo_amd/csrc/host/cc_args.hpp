@@ -1,6 +1,6 @@
 // cc_args.hpp -- the host half of congestion control (include/ugo_cc.h) that
 // needs no device: the argument rules of every ugo_fec_cc_* entry point and the
-// reference defaults.  Kept apart from ugo_fec.cpp as host/sent_args.hpp is.
+// reference defaults.  Kept apart from ugo_cc.cpp as host/sent_args.hpp is.
 #pragma once
 #include <cstddef>
 #include <cstdint>

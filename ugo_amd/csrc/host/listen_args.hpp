@@ -1,6 +1,6 @@
 // listen_args.hpp -- the host half of the connection table (include/ugo_listen.h)
 // that needs no device: the argument rules of every ugo_fec_listen_* entry point
-// and the slot count.  Kept apart from ugo_fec.cpp as host/cc_args.hpp is.
+// and the slot count.  Kept apart from ugo_listen.cpp as host/cc_args.hpp is.
 #pragma once
 #include <cstddef>
 #include <cstdint>

@@ -1,6 +1,6 @@
 // loop_args.hpp -- the host half of the connection loop (include/ugo_loop.h)
 // that needs no device: the argument rules of every ugo_fec_loop_* entry point
-// and the reference defaults.  Kept apart from ugo_fec.cpp as host/cc_args.hpp is.
+// and the reference defaults.  Kept apart from ugo_loop.cpp as host/cc_args.hpp is.
 #pragma once
 #include <cstddef>
 #include <cstdint>

@@ -1,7 +1,7 @@
 // sent_args.hpp -- the host half of the sent histories (include/ugo_sent.h)
 // that needs no device: the argument rules of every ugo_fec_sent_* entry point,
 // the layout of a history's device block and the build of a set's member and
-// chunk tables.  Kept apart from ugo_fec.cpp so that a stand-alone program can
+// chunk tables.  Kept apart from ugo_sent.cpp so that a stand-alone program can
 // run it under a sanitizer (tools/sent_args_check.cpp).
 #pragma once
 #include <algorithm>
@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../sent_kernels.hpp"
+#include "member_list.hpp"
 
 namespace ugo {
 namespace sentargs {
@@ -50,18 +51,14 @@ struct Member {
 
 // The rules of ugo_fec_sent_set_create; members[i] null for a NULL handle.
 inline bool members_ok(const void* ctx, const Member* const* members, size_t nconn) {
-  if (!ctx || !members || nconn == 0 || nconn > kern::kSentSetMaxConn) return false;
+  // (a history listed twice would be advanced twice)
+  if (nconn > kern::kSentSetMaxConn || !ugo::members::list_ok(ctx, members, nconn)) return false;
   uint64_t chunks = 0;
   for (size_t i = 0; i < nconn; ++i) {
-    if (!members[i] || members[i]->ctx != ctx || !members[i]->block || !window_ok(members[i]->window_packets) ||
-        !seg_cap_ok(members[i]->seg_cap))
-      return false;
+    if (!members[i]->block || !window_ok(members[i]->window_packets) || !seg_cap_ok(members[i]->seg_cap)) return false;
     chunks += members[i]->window_packets / kern::kSentChunk;
   }
-  if (chunks > (uint64_t(1) << 30)) return false;  // one block per chunk in a grid
-  std::vector<const Member*> sorted(members, members + nconn);  // a history listed twice would be advanced twice
-  std::sort(sorted.begin(), sorted.end());
-  return std::adjacent_find(sorted.begin(), sorted.end()) == sorted.end();
+  return chunks <= (uint64_t(1) << 30);  // one block per chunk in a grid
 }
 
 // One table entry per member, in set order, and the member of every chunk.

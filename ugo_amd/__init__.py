@@ -3,7 +3,12 @@
 The package holds only what that path needs:
   csrc/        gfx950 HIP kernels + the C-ABI, one ugo_*.cpp per public header
                (built into libugofec.so)
-  fec.py       host mirror of the reedsolomon.Encoder subset ugo uses
+  fec.py       host mirror of the reedsolomon.Encoder subset ugo uses: the import
+               surface of the ctypes binding
+  abi.py       the binding's base: the library and its prototypes, the errors, the
+               handle owner, the member-set base and the operand checks
+  encoder.py, stream.py, ack.py, sent.py, cc.py, listen.py, loop.py, fecconn.py
+               the binding, one module per public header of include/
   shard.py     multi-GPU partitioning of independent packet groups
 """
 from .fec import (  # noqa: F401

@@ -97,9 +97,11 @@
  *   (e) started is cleared by the call's highest acknowledged number, judged
  *       after the call's increments; the reference clears it per packet while
  *       still in slow start.  The value is read only in slow start.
- *   (f) the cube root is the integer root (the largest t with t^3 <= x); up to
- *       the reference's default maximum window it equals
- *       uint32(math.Cbrt(float64(x))).
+ *   (f) the cube root is the integer root (the largest t with t^3 <= x).  For
+ *       every difference last_max_cwnd - cwnd of 1 .. 2^20, the whole range
+ *       UGO_CC_MAX_CWND_LIMIT permits, it equals the restatement's
+ *       uint32(cbrt(float64(x))), which is numpy's cbrt; Go's own math.Cbrt has
+ *       not been run against it.
  *   (g) a budget counts packets of packet_bytes; a shorter packet still counts
  *       as one.
  *   (h) byte counts are 64-bit (the reference's are uint32).

@@ -12,6 +12,7 @@ import numpy as np
 import torch
 
 import cc_ref as cr
+import sent_ref as sr
 from sent_harness import M64, SentHarness, _i64, _put
 from ugo_amd import fec
 
@@ -33,6 +34,44 @@ def event_array(events):
     return out
 
 
+class _SentRulesOnly:
+    def __init__(self, wss, seg_caps):
+        self.rules = [sr.RuleSent(ws, seg_caps) for ws in wss]
+
+    def record(self, packets, now_us=None):
+        sr.record_set(self.rules, [(p[0], p[1] & M64, p[2], p[3], p[4], p[5] & M64, p[6]) for p in packets], now_us)
+
+
+class CcRulesOnly:
+    """What a driver uses of CcHarness (h.record, ack, rto, states, close) on
+    the rules alone: the conditions a device run must meet are held on the CPU
+    through the same generator and seeds."""
+
+    def __init__(self, wss, seg_caps=1, **params):
+        self.h = _SentRulesOnly(wss, seg_caps)
+        self.nconn = len(wss)
+        self.rules = [cr.RuleCc(**params) for _ in range(self.nconn)]
+
+    def ack(self, events, rows, now_us):
+        sent = self.h.rules
+        return [r.ack(events[c], rows[c], now_us, sent[c].last_sent, sent[c].lio, sent[c].err)
+                for c, r in enumerate(self.rules)]
+
+    def rto(self, fired, packet_bytes, max_budget):
+        sent = self.h.rules
+        return [r.rto(int(fired[c]), sent[c].last_sent, sent[c].bytes_in_flight, packet_bytes, max_budget, sent[c].err)
+                for c, r in enumerate(self.rules)]
+
+    def states(self):
+        out = np.zeros(self.nconn, fec.CC_STATE_DTYPE)
+        for k in cr.RuleCc.FIELDS:
+            out[k] = [getattr(r, k) & M64 for r in self.rules]
+        return out
+
+    def close(self):
+        pass
+
+
 class CcHarness:
     def __init__(self, enc, wss, seg_caps=1, watch=None, **params):
         self.h = SentHarness(enc, wss, seg_caps, watch=watch)
@@ -45,6 +84,9 @@ class CcHarness:
     def close(self):
         self.cc.close()
         self.h.close()
+
+    def states(self):
+        return self.cc.states()
 
     # ---------------------------------------------------------------- state
     def check(self, sent=False):

@@ -180,12 +180,13 @@ def _u16v(a):
 
 class ChainHarness(_Comparing):
     def __init__(self, enc, n, now, max_ranges, max_packets, max_exits=None, max_budget=8, max_entries=64,
-                 where="device", defer=False, delay=None, **loop_params):
+                 where="device", defer=False, delay=None, cc_params=None, **loop_params):
         assert not (defer and where == "pinned"), "a pinned clone is a host copy, not stream work"
         self._comparing(defer, delay)
         self.enc, self.where = enc, where
+        self.cc_params = dict(cc_params or {})
         self.rule = ch.RuleEndpoint(n, now, max_ranges, max_packets, max_exits=max_exits, max_budget=max_budget,
-                                    max_entries=max_entries, **loop_params)
+                                    max_entries=max_entries, cc_params=cc_params, **loop_params)
         self.loop_params = loop_params
         self.pad = torch.from_numpy(ch.pad_bytes()).cuda()
         self.rx = [fec.StreamRx(enc, ch.RX_CAP) for _ in range(n)]
@@ -215,7 +216,7 @@ class ChainHarness(_Comparing):
         self.n = n
         self.rset, self.aset = fec.StreamRxSet(enc, self.rx), fec.AckRxSet(enc, self.ack)
         self.tset, self.sset = fec.StreamTxSet(enc, self.tx), fec.SentTxSet(enc, self.sent)
-        self.cc = fec.CcSet(enc, self.sset)
+        self.cc = fec.CcSet(enc, self.sset, **self.cc_params)
         self.loop = fec.LoopSet(enc, self.rset, self.aset, self.tset, self.sset, now_us=now, **self.loop_params)
         self.sets = (self.loop, self.cc, self.rset, self.aset, self.tset, self.sset)
         dev = torch.device("cuda")

@@ -116,8 +116,9 @@ def _u64(values):
 
 class RuleEndpoint:
     def __init__(self, n, now, max_ranges, max_packets, max_segments=MS, max_exits=None, max_budget=8,
-                 max_entries=64, **loop_params):
+                 max_entries=64, cc_params=None, **loop_params):
         self.n, self.MR, self.NP, self.MSEG = n, max_ranges, max_packets, max_segments
+        self.cc_params = dict(cc_params or {})            # the congestion controllers'; none: the defaults
         self.max_exits = n if max_exits is None else max_exits
         self.max_budget, self.max_entries, self.loop_params = max_budget, max_entries, loop_params
         self.pad = pad_bytes()
@@ -139,7 +140,7 @@ class RuleEndpoint:
         """What LoopSet and CcSet keep in the set starts afresh with the set."""
         n = self.n
         self.loop = [lf.RuleLoop(now, **self.loop_params) for _ in range(n)]
-        self.cc = [cr.RuleCc() for _ in range(n)]
+        self.cc = [cr.RuleCc(**self.cc_params) for _ in range(n)]
         self.budget = self._cc_rto([0] * n)
         self.delays = [0] * n
 
@@ -517,7 +518,7 @@ def link(scr, state, side, rnd, out):
                 lost_fin=lost_fin, sender=out)
 
 
-def run_pair(scr, A, B, round_cap=200):
+def run_pair(scr, A, B, round_cap=200, start_us=START_US):
     """Both sides through the script.  A and B have RuleEndpoint's methods and
     fields.  The clock steps 20 ms a round; when a round sent nothing it jumps
     to the earlier of the two deadlines sent returned, which is how the timers
@@ -528,7 +529,7 @@ def run_pair(scr, A, B, round_cap=200):
     st = dict(rounds=0, trunc_acks=0, retx_delivered=0, late=0, pending_rounds=0, over_exits=0, lost_fin=0, ack_only=0,
               fired=0, fin_round=[{}, {}], data_round=[{}, {}], reasons=[{}, {}], done=False)
     closed = [set(), set()]
-    now = START_US
+    now = start_us
     for rnd in range(1, round_cap + 1):
         st["rounds"] = rnd
         sent_any = False

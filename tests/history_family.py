@@ -25,6 +25,10 @@ from the consumer's rules: the stop-waiting attach handed out, and the number
 of queued segments a drain is sized by.  run() counts what the traffic reached
 (Family.stats); describe() replays a family on the rules alone up to one call
 and prints that call's inputs per member.
+
+Every clock of a run is start_us plus what the script adds.  EDGE is 2^32 us:
+run() counts the RTT samples, the RTOs and the receive side's lo_time_us that
+reach across it, for the runs that start just below it.
 """
 import random
 from collections import Counter
@@ -44,11 +48,13 @@ P_ROUND_LOST, P_SWAP, P_SACK, P_AGAIN = 0.07, 0.05, 0.6, 0.03
 P_RTO, P_DRAIN, P_HALF = 0.15, 0.85, 0.5
 RTO_STEP_US = 600_000
 START_US = 1_000_000
+EDGE = 1 << 32
 
 
 class Family:
-    def __init__(self, seed, max_ranges, nconn=24, rounds=20, seg_cap=2):
+    def __init__(self, seed, max_ranges, nconn=24, rounds=20, seg_cap=2, start_us=START_US):
         self.seed, self.max_ranges, self.nconn, self.rounds, self.seg_cap = seed, max_ranges, nconn, rounds, seg_cap
+        self.start_us = start_us
         rng = self.rng = random.Random(seed)
         self.wss = [rng.choice(WINDOWS) for _ in range(nconn)]
         self.first = [rng.choice(FIRSTS) for _ in range(nconn)]
@@ -64,7 +70,8 @@ class Family:
         self.stats = Counter()
 
     def __repr__(self):
-        return f"family seed {self.seed}, max_ranges {self.max_ranges}, {self.nconn} members, {self.rounds} rounds"
+        at = "" if self.start_us == START_US else f", from {self.start_us} us"
+        return f"family seed {self.seed}, max_ranges {self.max_ranges}, {self.nconn} members, {self.rounds} rounds{at}"
 
     # ---------------------------------------------------------------- attach
     def plan(self):
@@ -279,7 +286,7 @@ class DeviceCcOps(DeviceOps):
 
     def __init__(self, ch, max_ranges):
         DeviceOps.__init__(self, ch.h)
-        self.ch = ch
+        self.ch, self.cc = ch, ch.rules
         self.fired, self.max_ranges = [], max_ranges
 
     def ack(self, packets, max_ranges, now_us):
@@ -386,7 +393,12 @@ def run(fam, ops, rx=None, stop=None, out=None):
     re-raised as FamilyFailure naming seed, round and call.  stop = (round,
     call name): return before that call, after describing it to out."""
     rng, st, rules = fam.rng, fam.stats, ops.rules
-    now = START_US
+    now = fam.start_us
+    st["first_clock"] = now
+
+    def across(pre_sent_us, fired, t):
+        """RTOs that fired at t >= EDGE on a last_sent_us from below it."""
+        st["rto_across"] += sum(1 for f, u in zip(fired, pre_sent_us) if f and 0 < u < EDGE <= t)
 
     def call(r, name, fn, *args):
         if stop == (r, name):
@@ -400,7 +412,8 @@ def run(fam, ops, rx=None, stop=None, out=None):
             raise FamilyFailure(f"{fam}: round {r}, call {name}: {type(e).__name__}: {e}\n"
                                 f"replay without a GPU: history_family.describe({fam.seed}, {fam.max_ranges}, "
                                 f"{fam.nconn}, {fam.rounds}, {r}, {name!r}, cc={isinstance(ops, (RuleCcOps, DeviceCcOps))}, "
-                                f"rx={rx is not None})"
+                                f"rx={rx is not None}" + ("" if fam.start_us == START_US else f", start_us={fam.start_us}")
+                                + ")"
                                 ) from e
 
     try:
@@ -421,7 +434,9 @@ def run(fam, ops, rx=None, stop=None, out=None):
                 for i in range(0, len(arrivals), 64):
                     st["rx_mixed_stretches"] += len({p[1] for p in arrivals[i:i + 64]}) >= 5
                 plan = fam.rx_plan(rx.rules)
+                lo_times = [x.lo_time_us for x in rx.rules]
                 att = call(r, "ack_attach", rx.attach, *plan[:4], fam.max_ranges, plan[4], now + 1500)
+                st["lo_time_across"] += sum(1 for a, u in zip(att, lo_times) if a and 0 < u < EDGE <= now + 1500)
                 st["rx_truncated"] += sum(1 for a in att if a == ar.TRUNCATED)
                 st["rx_attached"] += sum(1 for a in att if a)
             accepted = _note_acks(fam, acks, rules)
@@ -429,7 +444,10 @@ def run(fam, ops, rx=None, stop=None, out=None):
             # the first number set_ack scans (never more than a window below last_sent), and what is queued
             pre2 = [(max(lo, hi - x.ws + 1, 1), [n for n, s in x.slots.items() if s["state"] == sr.QUEUED])
                     for x, (lo, hi) in zip(rules, pre)]
+            sent_us = [x.last_sent_us for x in rules]
             ev = call(r, "ack", ops.ack, acks, fam.max_ranges, now + 1000)
+            st["rtt_across"] += sum(1 for e in ev if e["has_rtt"] and now + 1000 - int(e["rtt_us"]) < EDGE <= now + 1000)
+            across(sent_us, getattr(ops, "fired", []), now + 1000)
             for c, (lo, hi) in enumerate(pre):
                 st["long_spans"] += bool(ev[c]["accepted"] and hi - lo + 1 > 1024)
                 assert bool(ev[c]["accepted"]) == bool(accepted[c]), (c, "the script's own reading of set_ack is off")
@@ -438,7 +456,10 @@ def run(fam, ops, rx=None, stop=None, out=None):
             if rng.random() < P_RTO:
                 delays = [rng.choice((0, 0, 100_000, 300_000)) for _ in rules]
                 now += RTO_STEP_US
-                fired = [a or b for a, b in zip(call(r, "rto", ops.rto, delays, now + 1000), fired or [0] * fam.nconn)]
+                sent_us = [x.last_sent_us for x in rules]
+                again = call(r, "rto", ops.rto, delays, now + 1000)
+                across(sent_us, again, now + 1000)
+                fired = [a or b for a, b in zip(again, fired or [0] * fam.nconn)]
             st["rtos"] += sum(fired)
             if rng.random() < P_DRAIN:
                 m = sum(x.queued_segments for x in rules if not x.err)
@@ -448,6 +469,8 @@ def run(fam, ops, rx=None, stop=None, out=None):
                 st["clamped_drains"] += any(x.queued for x in rules if not x.err)
     except _Stop:
         return st
+    st["last_clock"] = now + 1000
+    st["cutbacks"] = sum(k.cutbacks for k in getattr(ops, "cc", []))
     live = [c for c, x in enumerate(rules) if not x.err]
     st["inert"] = fam.nconn - len(live)
     st["inert_peers"] = sum(1 for p in fam.peers if p.err)
@@ -499,9 +522,9 @@ def _describe(fam, r, name, args, ops, rx, out):
         p("packets of no member:", other)
 
 
-def describe(seed, max_ranges, nconn, rounds, r, name, cc=False, rx=False, out=None):
+def describe(seed, max_ranges, nconn, rounds, r, name, cc=False, rx=False, out=None, start_us=START_US):
     """Replays the family on the rules alone up to call `name` of round r and
     prints that call's inputs and every member's record before it.  rx: the
     family also fed a receiving consumer (which draws from the same seed)."""
-    fam = Family(seed, max_ranges, nconn, rounds)
+    fam = Family(seed, max_ranges, nconn, rounds, start_us=start_us)
     run(fam, RuleCcOps(fam) if cc else RuleOps(fam), RuleRx(fam) if rx else None, stop=(r, name), out=out)

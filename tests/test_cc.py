@@ -4,6 +4,7 @@ import ctypes
 import random
 import re
 import time
+from collections import Counter
 
 import numpy as np
 import pytest
@@ -11,6 +12,7 @@ import pytest
 import ack_ref as ar
 import cc_ref as cr
 import sent_ref as sr
+from cc_harness import CcHarness, CcRulesOnly, event_array, row_array
 from sent_ref import Ack
 from ugo_amd import fec
 
@@ -203,11 +205,237 @@ def test_deviation_i_the_rto_takes_the_candidate_cc_set_ack_saw():
 
 
 def test_the_integer_cube_root_is_the_references_up_to_its_default_window():
+    """... and up to the largest window the header permits: every difference
+    last_max_cwnd - cwnd of 1 .. 2^20, against the restatement's root, which is
+    numpy.cbrt on float64 (Go's own math.Cbrt is not what this compares with)."""
     for d in range(1, 200):
         x = cr.CUBE_FACTOR * d
         t = cr.icbrt(x)
         assert t ** 3 <= x < (t + 1) ** 3 and t == cr.cbrt_go(x), d
     assert cr.icbrt(0) == 0 and cr.icbrt(7) == 1 and cr.icbrt(8) == 2 and cr.icbrt((1 << 64) - 1) == 2642245
+    x = np.uint64(cr.CUBE_FACTOR) * np.arange(1, (1 << 20) + 1, dtype=np.uint64)      # below 2^52: exact as float64
+    t = np.zeros_like(x)
+    for b in range(21, -1, -1):                            # cr.icbrt, every difference at once
+        cand = t | np.uint64(1 << b)
+        t = np.where(cand * cand * cand <= x, cand, t)     # cand < 2^21.4: the cube stays below 2^64
+    assert int(t[-1]) == cr.icbrt(int(x[-1])) == 141_147 and int(t[198]) == cr.icbrt(int(x[198]))
+    assert bool((t * t * t <= x).all()) and bool((x < (t + np.uint64(1)) ** np.uint64(3)).all())
+    bad = np.flatnonzero(t != np.cbrt(x.astype(np.float64)).astype(np.uint64))
+    assert bad.size == 0, (bad[:8] + 1, t[bad[:8]])
+
+
+# ---------------------------------------------------------------- CPU: off the defaults, event by event
+# (initial_cwnd, max_cwnd, min_cwnd, num_connections, mss)
+PARAM_SETS = {
+    "defaults": dict(cr.DEFAULTS),
+    "window_2_20": dict(initial_cwnd=32, max_cwnd=1 << 20, min_cwnd=2, num_connections=1, mss=1460),
+    "jumbo": dict(initial_cwnd=1000, max_cwnd=100_000, min_cwnd=1, num_connections=8, mss=9000),
+    "floor_2_19": dict(initial_cwnd=1 << 20, max_cwnd=1 << 20, min_cwnd=1 << 19, num_connections=1000, mss=1),
+}
+# floor_2_19 is never in slow start: its window starts at ssthresh = max_cwnd, a cutback sets ssthresh = cwnd,
+# and an RTO leaves ssthresh = cwnd / 2 <= 2^19 = min_cwnd = cwnd.  The tests below hold that instead.
+NEVER_IN_SLOW_START = ("floor_2_19",)
+CLOCK_STEPS = (1000, 20_000, 30_000, 30_001, 200_000, 5 * 10 ** 6, 4 * 10 ** 8, 36 * 10 ** 8, 10 ** 13)
+STEP_WEIGHTS = (4, 6, 3, 3, 4, 3, 3, 1, 1)
+SHORT_STEPS = CLOCK_STEPS[:6]                              # each twice: 12 rounds stay below 10^8 us
+ACKED = (0, 1, 3, 40, 300, 5000, 60_000)
+ACKED_WEIGHTS = (2, 4, 4, 5, 4, 3, 2)
+WRAP_OFFSET = 282_000                                     # 410 * offset^3 passes 2^63 from here on
+
+
+def _wide_fields(rng, rule):
+    """What of an event row does not depend on packet numbers: an even RTT
+    sample and ACK delay (deviation (c)), bytes in flight around the member's
+    own window and far above it."""
+    mss = rule.p["mss"]
+    w = rule.cwnd * mss
+    bif = rng.choice((0, w // 2, w // 2 + 1, w - 3 * mss - 1, w - 3 * mss, w - 1, w, w + 1, 2 * w, 10 ** 12, 1 << 62))
+    return dict(accepted=int(rng.random() < 0.9), has_rtt=int(rng.random() < 0.8),
+                rtt_us=2 * (rng.choice((0, 450, 2000, 10_000, 10_500, 30_000, 1_250_000)) + rng.randrange(25)),
+                delay_us=rng.choice((0, 10, 3000, 10 ** 7)), bytes_in_flight=max(bif, 0),
+                acked_packets=rng.choices(ACKED, ACKED_WEIGHTS)[0], lost_packets=rng.choice((0, 0, 0, 0, 0, 1, 3)))
+
+
+def _cubic_offset(rule, now):
+    """time_to_origin - elapsed of the call's CUBIC step, if it took one past
+    the 30-ms return (the fields are as that step left them)."""
+    if rule.last_update_us != now or rule.epoch_us == 0:
+        return 0
+    return rule.time_to_origin - cr.go_div(cr.s64((now + rule.min_rtt_us - rule.epoch_us) << 10), 1000000)
+
+
+def _go_budget(go, bif, packet_bytes, max_budget):
+    k = 0
+    while k < max_budget and bif <= go.GetCongestionWindow():
+        k, bif = k + 1, bif + packet_bytes
+    return k
+
+
+def _views_differ(go, rule):
+    g, r = go.view(), rule.view()
+    return [k for k in g if g[k] != r[k] and (k != "started" or (g["cwnd"] < g["ssthresh"] and
+                                                                   r["cwnd"] < r["ssthresh"]))]
+
+
+def run_events(seed, reach, **params):
+    """One seeded sequence of synthetic event and cc rows into RuleCc.ack beside
+    GoCubicSender.UpdateRTT / OnCongestionEvent, and RTOs as checkRTO makes
+    them beside RuleCc.rto.  The numbers a call acknowledges and loses are
+    n_from + 1 .. hi, acknowledged in rising order.  Returns the calls compared."""
+    rng = random.Random(seed)
+    now = [2 * rng.randrange(500, 500_000)]
+    go, rule = cr.GoCubicSender(lambda: now[0] * cr.US, **params), cr.RuleCc(**params)
+    n_from = last_sent = compared = 0
+    for _ in range(rng.randint(10, 24)):
+        now[0] += rng.choices(CLOCK_STEPS, STEP_WEIGHTS)[0]
+        ev = _wide_fields(rng, rule)
+        acked, nlost = ev["acked_packets"], ev["lost_packets"]
+        hi = n_from + acked + nlost
+        lost = sorted(rng.sample(range(n_from + 1, hi + 1), nlost)) if acked + nlost else []
+        nlost = ev["lost_packets"] = len(lost)
+        last_sent = max(last_sent, hi + rng.choice((0, 3, 40)))
+        lio = rng.choice((last_sent, hi, max(n_from - 5, 0)))
+        below = max(0, min(rule.cutback, hi) - n_from)    # numbers of this call at or below the cutback
+        row = dict(max_lost=max(lost, default=0), max_acked=max((n for n in (hi, hi - 1, hi - 2, hi - 3)
+                                                                 if n > n_from and n not in lost), default=0),
+                   acked_le=below - sum(1 for n in lost if n <= rule.cutback))
+        ev["largest_acked"] = row["max_acked"]
+        go.OnPacketSent(last_sent)
+        if ev["accepted"]:
+            if ev["has_rtt"]:
+                go.UpdateRTT(ev["rtt_us"] * cr.US, ev["delay_us"] * cr.US)
+            gone = set(lost)
+            go.OnCongestionEvent(bool(ev["has_rtt"]), ev["bytes_in_flight"],
+                                 [n for n in range(n_from + 1, hi + 1) if n not in gone], lost)
+            n_from = hi
+        delay = rule.ack(ev, row, now[0], last_sent, lio)
+        assert delay == go.RetransmissionDelay() // cr.US
+        assert not _views_differ(go, rule), (seed, params, compared, "ack", _views_differ(go, rule))
+        reach["slow start" if rule.in_slow_start() else "avoidance"] += 1
+        reach["max_cwnd"] = max(reach["max_cwnd"], rule.cwnd)
+        reach["max_time_to_origin"] = max(reach["max_time_to_origin"], rule.time_to_origin)
+        reach["wrapped_cubes"] += abs(_cubic_offset(rule, now[0])) >= WRAP_OFFSET
+        fired = int(rng.random() < 0.12)
+        if fired:
+            if rule.rto_candidate != 0 and rule.rto_candidate > go.largestSentAtLastCutback:
+                go.onPacketLost(rule.rto_candidate)
+            go.OnRetransmissionTimeout(True)
+        bif, pb, mb = rng.choice((0, 1400, rule.cwnd * rule.p["mss"], 10 ** 12)), rng.choice((1, 1400, 9000)), \
+            rng.choice((0, 8, 64))
+        assert rule.rto(fired, last_sent, bif, pb, mb) == _go_budget(go, bif, pb, mb)
+        assert not _views_differ(go, rule), (seed, params, compared, "rto", _views_differ(go, rule))
+        compared += 1
+    reach["cutbacks"] += rule.cutbacks
+    reach["rtos"] += rule.rtos
+    return compared
+
+
+EVENT_SEEDS = range(40)
+
+
+@pytest.mark.parametrize("name", list(PARAM_SETS))
+def test_events_off_the_defaults_equal_the_reference(name):
+    """Conditions on the generator, not measurements: what its seeds reach on
+    the rules alone.  Printed, then held."""
+    reach = Counter()
+    total = sum(run_events(seed, reach, **PARAM_SETS[name]) for seed in EVENT_SEEDS)
+    print(name, "calls compared", total, dict(reach))
+    assert reach["avoidance"] > 0 and reach["cutbacks"] > 0 and reach["rtos"] > 0
+    assert (reach["slow start"] > 0) != (name in NEVER_IN_SLOW_START)
+    assert reach["wrapped_cubes"] > 0
+    if name == "window_2_20":
+        assert reach["max_cwnd"] >= 1 << 19
+    # defaults: at most icbrt(cubeFactor * 199) = 8,108; floor_2_19: beta is 0.9997, a cutback takes 314 at the most
+    if name in ("window_2_20", "jumbo"):
+        assert reach["max_time_to_origin"] >= 1 << 14
+
+
+# ---------------------------------------------------------------- every mode at once, off the defaults
+# The driver of the device tests; CcRulesOnly runs it without a device, so that what the seeds reach is held
+# here first.  T1 crosses 2^32 us in mid-run; T4 ends 10^8 us short of 2^64 and takes the short steps only.
+EVERY_MODE_MEMBERS, EVERY_MODE_ROUNDS = 257, 12            # two blocks, the second with one lane
+T1, T4 = (1 << 32) - (sum(SHORT_STEPS) + 2500), (1 << 64) - 10 ** 8    # T1: the seventh call is the first past 2^32
+EVERY_MODE = [(name, 0, "long") for name in PARAM_SETS] + [("defaults", T1, "short"), ("defaults", T4, "short")]
+EVERY_MODE_IDS = [f"{name}-{'0' if not base else 'T1' if base == T1 else 'T4'}" for name, base, _ in EVERY_MODE]
+BUDGET_BYTES, BUDGET_MAX = (1, 1400, 9000), (0, 8, 64, 1 << 31)
+
+
+def _wide_event(rng, rule, n_from):
+    """An event row and a cc row as ugo_fec_cc_sent_ack could write them, off
+    the generator of run_events."""
+    ev = _wide_fields(rng, rule)
+    acked, lost, mss = ev["acked_packets"], ev["lost_packets"], rule.p["mss"]
+    hi = n_from + acked + lost
+    ev.update(acked_bytes=mss * acked, lost_bytes=mss * lost, largest_acked=hi)
+    row = dict(max_lost=rng.randrange(n_from, hi + 1) if lost else 0, max_acked=hi if acked else 0,
+               acked_le=rng.randrange(0, acked + 1))
+    return ev, row
+
+
+def drive_every_mode(h, name, base, steps):
+    """The body of test_controller_equals_the_rule_in_every_mode_at_once with
+    the wide generator, every clock above base.  h: a CcHarness or a
+    CcRulesOnly.  Returns the clocks of the calls and the wrapped cubes met."""
+    nconn = h.nconn
+    rng = random.Random(f"{name} {base}")
+    pk = [(c, n, 1000 + 100 * (c % 5), 0, 0, 0, [(10 * n, 10)], None) for c in range(nconn) if c % 7 != 6
+          for n in range(1, 2 + c % 4)]
+    pk.append((1, 5000, 10, 0, 0, 0, [], None))                             # member 1 becomes inert
+    h.h.record(pk, now_us=base + 1000)
+    n_from = [1] * nconn
+    now, clocks, wrapped = base + 2000, [], 0
+    if steps == "long":                                                    # every step once, three of them twice
+        schedule = list(CLOCK_STEPS) + rng.choices(CLOCK_STEPS, STEP_WEIGHTS, k=EVERY_MODE_ROUNDS - len(CLOCK_STEPS))
+        rng.shuffle(schedule)
+    else:
+        schedule = list(SHORT_STEPS) * 2
+    for step in schedule:
+        now += step
+        clocks.append(now)
+        evs, rows = [], []
+        for c in range(nconn):
+            ev, row = _wide_event(rng, h.rules[c], n_from[c])
+            n_from[c] = max(n_from[c], ev["largest_acked"])
+            evs.append(ev), rows.append(row)
+        h.ack(event_array(evs), row_array(rows), now)
+        wrapped += sum(abs(_cubic_offset(x, now)) >= WRAP_OFFSET for x in h.rules)
+        h.rto([int(rng.random() < 0.15) for _ in range(nconn)], rng.choice(BUDGET_BYTES), rng.choice(BUDGET_MAX))
+    return clocks, wrapped
+
+
+def hold_every_mode(st, name, base, clocks, where):
+    """What the records of a run show at its end; the same of the rules alone
+    and of ugo_fec_cc_set_state."""
+    p = PARAM_SETS[name]
+    live = st[np.arange(len(st)) != 1]
+    slow = live["cwnd"] < live["ssthresh"]
+    reach = dict(slow_start=int(slow.sum()), avoidance=int((~slow).sum()),
+                 cutbacks=int(live["cutbacks"].sum()), rtos=int(live["rtos"].sum()),
+                 app_limited=int(np.count_nonzero(live["app_limited_us"])),
+                 epochs=int(np.count_nonzero(live["epoch_us"])), max_cwnd=int(live["cwnd"].max()),
+                 max_time_to_origin=int(live["time_to_origin"].max()))
+    print(where, name, "base", base, "clocks", clocks[0], "..", clocks[-1], reach)
+    assert reach["avoidance"] and reach["cutbacks"] and reach["rtos"] and reach["app_limited"] and reach["epochs"]
+    assert bool(reach["slow_start"]) != (name in NEVER_IN_SLOW_START)
+    if name == "window_2_20":
+        assert reach["max_cwnd"] >= 1 << 19 and reach["max_time_to_origin"] >= 1 << 14
+    assert st["cwnd"][1] == p["initial_cwnd"] and st["cutbacks"][1] == 0 and st["rtos"][1] == 0          # inert
+    assert base + 2000 < clocks[0] and clocks[-1] < 1 << 64
+    if base == T1:
+        below = sum(1 for t in clocks if t < 1 << 32)
+        assert 3 <= below <= len(clocks) - 3, clocks                         # 2^32 falls in mid-run
+    if base == T4:
+        assert min(int(x) for x in live["epoch_us"] if x) > T4               # no clock wrapped to a small one
+
+
+@pytest.mark.parametrize("name,base,steps", EVERY_MODE, ids=EVERY_MODE_IDS)
+def test_every_mode_runs_reach_what_they_are_for(name, base, steps):
+    """The rules alone through the generator and seeds of the device tests."""
+    h = CcRulesOnly([1024] * EVERY_MODE_MEMBERS, 1, **PARAM_SETS[name])
+    clocks, wrapped = drive_every_mode(h, name, base, steps)
+    hold_every_mode(h.states(), name, base, clocks, "rules alone:")
+    print("   wrapped cubes", wrapped)
+    assert wrapped > 0 or steps == "short"
 
 
 def _closed_form(setup, calls):
@@ -338,7 +566,6 @@ def test_argument_errors_that_need_no_launch():
 # ---------------------------------------------------------------- GPU
 import torch  # noqa: E402
 
-from cc_harness import CcHarness, event_array, row_array  # noqa: E402
 from sent_harness import NO_CONN, _put  # noqa: E402
 
 M64 = (1 << 64) - 1
@@ -464,6 +691,152 @@ def test_controller_equals_the_rule_in_every_mode_at_once(enc, nconn):
         assert (live["cwnd"] < live["ssthresh"]).any() and (live["cwnd"] >= live["ssthresh"]).any()
         assert live["cutbacks"].any() and live["rtos"].any() and live["app_limited_us"].any() and live["epoch_us"].any()
         assert st["cwnd"][1] == 32 and st["cutbacks"][1] == 0 and st["rtos"][1] == 0          # inert
+    h.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name,base,steps", EVERY_MODE, ids=EVERY_MODE_IDS)
+def test_controller_equals_the_rule_in_every_mode_at_once_off_the_defaults(enc, name, base, steps):
+    """257 members (two blocks, the second with one lane) through
+    drive_every_mode: large counts, bytes in flight around each member's own
+    window, idle times up to 10^13 us, budgets up to 2^31 -- per parameter set,
+    and at the defaults across 2^32 us and just below 2^64."""
+    n = EVERY_MODE_MEMBERS
+    h = CcHarness(enc, [1024] * n, 1, watch=[0, n - 1], **PARAM_SETS[name])
+    try:
+        clocks, _ = drive_every_mode(h, name, base, steps)
+        hold_every_mode(h.states(), name, base, clocks, "device:")
+    finally:
+        h.close()
+
+
+BOUNDARY_SETS = {"defaults": PARAM_SETS["defaults"], "jumbo": PARAM_SETS["jumbo"],
+                 "small": dict(initial_cwnd=10, max_cwnd=60, min_cwnd=3, num_connections=1, mss=1000)}
+
+
+def _boundary_table(cwnd, mss):
+    """(bytes_in_flight, acked_packets) around every edge of isCwndLimited for
+    a window of cwnd packets, and around half of cwnd + 5 packets: there the
+    closed form's ceil(2 bif / mss) decides where slow start stops."""
+    w, k = cwnd * mss, cwnd + 5
+    bifs = [w - 3 * mss - 1, w - 3 * mss, w - 3 * mss + 1, w // 2 - 1, w // 2, w // 2 + 1, w - 1, w, w + 1, 0,
+            k * mss // 2 - 1, k * mss // 2, k * mss // 2 + 1]
+    return [(b, g) for b in bifs for g in (1, 2, 50, 1000)]
+
+
+def _table_call(h, table, now):
+    evs = event_array([dict(accepted=1, acked_packets=g, bytes_in_flight=b) for b, g in table])
+    rows = np.zeros(len(table), fec.CC_ROW_DTYPE)
+    rows["max_acked"] = now
+    h.ack(evs, rows, now)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", list(BOUNDARY_SETS))
+def test_the_window_limit_boundaries_off_the_defaults(enc, name):
+    p = BOUNDARY_SETS[name]
+    table = _boundary_table(p["initial_cwnd"], p["mss"])
+    h = CcHarness(enc, [1024] * len(table), 1, watch=[0], **p)             # slow start
+    _table_call(h, table, 1_000_000)
+    grown = [r.cwnd - p["initial_cwnd"] for r in h.rules]
+    assert 0 in grown and max(grown) >= 5 and any(r.app_limited_us for r in h.rules), grown
+    assert len({g for g in grown if 0 < g < 50}) >= 3                      # stops at ssthresh aside, the stops differ
+    h.close()
+    # cut back once: cwnd == ssthresh.  The table of the first window and that of the window the cut left
+    h = CcHarness(enc, [1024] * 2 * len(table), 1, watch=[0], **p)
+    rows = np.zeros(h.nconn, fec.CC_ROW_DTYPE)
+    rows["max_lost"] = 1
+    h.ack(event_array([dict(accepted=1, lost_packets=1)] * h.nconn), rows, 1_000_000)
+    cut = h.rules[0].cwnd
+    assert all(r.cwnd == r.ssthresh == cut and r.cutbacks == 1 for r in h.rules) and cut < p["initial_cwnd"]
+    both = table + _boundary_table(cut, p["mss"])
+    for now in (1_050_000, 1_070_000, 1_101_000):                           # a new epoch, the 30-ms return, past it
+        _table_call(h, both, now)
+    assert any(r.cwnd > cut for r in h.rules) and any(r.cwnd == cut and r.app_limited_us for r in h.rules)
+    assert any(r.last_update_us == 1_101_000 for r in h.rules)
+    h.close()
+
+
+HYSTART_MIN_RTTS = (31_992, 32_000, 32_008, 64_000, 127_992, 128_000, 128_008, 10 ** 6)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("initial_cwnd", [15, 16])
+def test_hybrid_slow_starts_threshold_at_both_clamps_and_the_low_window(enc, initial_cwnd):
+    """min_rtt >> 3 is 3,999, 4,000, 4,001, 8,000, 15,999, 16,000, 16,001 and
+    125,000: below, at and above both clamps.  Members 0-7 see a round of eight
+    samples whose minimum is min_rtt + thr (not found), members 8-15 one whose
+    minimum is min_rtt + thr + 1 (found).  No event acknowledges a packet but
+    the first, which is app-limited, so the window never grows: at 15 the low
+    window holds the exit back in the round that finds it, at 16 it does not."""
+    thr = [max(min(m >> 3, 16_000), 4000) for m in HYSTART_MIN_RTTS]
+    assert thr == [4000, 4000, 4001, 8000, 15_999, 16_000, 16_000, 16_000]
+    mins, thrs = HYSTART_MIN_RTTS * 2, thr * 2
+    h = CcHarness(enc, [1024] * 16, 1, watch=[0], initial_cwnd=initial_cwnd)
+    # the sample that sets min_rtt; its packet is past end_packet_number (0), so the round it began ends with it
+    rows = np.zeros(16, fec.CC_ROW_DTYPE)
+    rows["max_acked"] = 1
+    h.ack(event_array([dict(accepted=1, has_rtt=1, rtt_us=m, acked_packets=1) for m in mins]), rows, 1_000_000)
+    assert all(r.started == 0 and r.cwnd == initial_cwnd and r.min_rtt_us == m for r, m in zip(h.rules, mins))
+    none = np.zeros(16, fec.CC_ROW_DTYPE)
+    for k in range(8):                                                      # the minimum comes as the sixth sample
+        extra = [(c >= 8) + (0 if k == 5 else 100 * (1 + (3 * k + c) % 7)) for c in range(16)]
+        evs = event_array([dict(accepted=1, has_rtt=1, rtt_us=m + t + x) for m, t, x in zip(mins, thrs, extra)])
+        h.ack(evs, none, 1_010_000 + 10_000 * k)
+    assert [r.found for r in h.rules] == [0] * 8 + [1] * 8 and all(r.sample_count == 8 for r in h.rules)
+    assert [r.current_min_rtt_us - r.min_rtt_us for r in h.rules] == thr + [t + 1 for t in thr]
+    low = initial_cwnd < 16
+    assert [r.ssthresh for r in h.rules] == [200] * 8 + [200 if low else 16] * 8
+    # the next sample of a round that found it leaves slow start whatever the window (the reference's own order)
+    h.ack(event_array([dict(accepted=1, has_rtt=1, rtt_us=m + 1) for m in mins]), none, 1_100_000)
+    assert [r.ssthresh for r in h.rules] == [200] * 8 + [initial_cwnd] * 8
+    h.close()
+
+
+@pytest.mark.gpu
+def test_rtt_filter_magnitudes(enc):
+    """Samples from 2^10 to 2^40 us, delays above the sample (kept whole) and
+    one below it (a sample of 1): the float32 lines of the rule, whose operands
+    stay below 2^53 and so reach float32 in one rounding."""
+    cases = []
+    for m in (1 << 10, (1 << 24) + 1, 1 << 27, (1 << 32) + 12_345, (1 << 40) + 3):
+        up = m + m // 3 + 1
+        cases += [((m, 0), (up, 0), (m, 0)), ((up, 0), (m, 0), (up, 1)), ((m, m + 5), (m // 2 + 7, m // 2 + 6), (m, 0)),
+                  ((m, m - 1), (m, 0), (m, m)), ((m, 0), (m, m - 1), (up, up + 1))]
+    h = CcHarness(enc, [1024] * len(cases), 1, watch=[0])
+    for k in range(3):
+        h.ack(event_array([dict(accepted=1, has_rtt=1, rtt_us=c[k][0], delay_us=c[k][1]) for c in cases]),
+              np.zeros(len(cases), fec.CC_ROW_DTYPE), 1_000_000 * (k + 1))
+        if k == 0:                                                          # after (m, m + 5); after (m, m - 1)
+            assert h.rules[2].latest_rtt_us == 1 << 10 and h.rules[3].srtt_us == 1 and h.rules[3].min_rtt_us == 1 << 10
+    assert max(r.srtt_us for r in h.rules) > 1 << 40 and h.rules[-1].latest_rtt_us == cases[-1][2][0] > 1 << 40
+    h.close()
+
+
+@pytest.mark.gpu
+def test_acked_count_wraps_as_a_uint32(enc):
+    """acked_packets is a uint32 of the event row, so one call adds 2^32 - 1 at
+    the most.  Member 0 takes that twice within 30 ms of a CUBIC step: the second
+    wraps acked_count.  Member 1 takes it once and then a step past the 30-ms
+    return, which turns a count of almost 2^32 into est_tcp_cwnd."""
+    big = (1 << 32) - 1
+    h = CcHarness(enc, [1024] * 2, 1)
+    rows = np.zeros(2, fec.CC_ROW_DTYPE)
+    rows["max_lost"] = 1
+    h.ack(event_array([dict(accepted=1, lost_packets=1)] * 2), rows, 1_000_000)      # avoidance at 27
+    rows = np.zeros(2, fec.CC_ROW_DTYPE)
+    rows["max_acked"] = 5
+
+    def call(g0, g1, now):
+        h.ack(event_array([dict(accepted=1, acked_packets=g, bytes_in_flight=1 << 62) for g in (g0, g1)]), rows, now)
+
+    call(big, big - 10, 1_050_000)
+    before = [r.acked_count for r in h.rules]
+    assert before == [big, big - 10] and all(r.cwnd < 200 for r in h.rules), before
+    call(big, 0, 1_060_000)                                                 # the 30-ms return
+    assert h.rules[0].acked_count == (before[0] + big) & 0xffffffff == before[0] - 1
+    call(3, 3, 1_100_000)
+    assert h.rules[1].est_tcp_cwnd > 50_000 and h.rules[1].cwnd == 200 and h.rules[1].acked_count < 1 << 20
     h.close()
 
 

@@ -23,13 +23,18 @@ SERVER = dict(seed=4, n=40, max_conn=64, max_ranges=8, max_packets=96, max_exits
 ROUND_CAP = 200
 
 
-def run(name, make):
+# The n = 3 run once more with other congestion parameters (the family of tests/test_cc.py) from a wall clock.
+OTHER_CC = dict(initial_cwnd=10, max_cwnd=60, min_cwnd=3, num_connections=1, mss=1000)
+WALL_CLOCK_US = 1_760_000_000_000_000
+
+
+def run(name, make, start_us=ch.START_US, **more):
     """The run `name` with make(n, now, **capacities) as both endpoints.  Returns (script, A, B, stats)."""
-    kw = dict(RUNS[name])
+    kw = dict(RUNS[name], **more)
     scr = ch.script(kw.pop("seed"), kw["n"])
     n = kw.pop("n")
-    A, B = make(n, ch.START_US, idle_us=scr.idle_us, **kw), make(n, ch.START_US, idle_us=scr.idle_us, **kw)
-    return scr, A, B, ch.run_pair(scr, A, B, round_cap=ROUND_CAP)
+    A, B = make(n, start_us, idle_us=scr.idle_us, **kw), make(n, start_us, idle_us=scr.idle_us, **kw)
+    return scr, A, B, ch.run_pair(scr, A, B, round_cap=ROUND_CAP, start_us=start_us)
 
 
 def lives_hold(scr, A, B, st):
@@ -87,6 +92,11 @@ def test_the_script_reaches_what_it_is_for():
     for name in ("n3", "n257", "mr2", "mr3", "clamp"):                             # packets arrive for exited members
         assert stats[name]["late"] > 0, name
     server_holds(run_server(ch.RuleServer, False)[1])
+    scr, A, B, st = run("n3", ch.RuleEndpoint, WALL_CLOCK_US, cc_params=OTHER_CC)
+    lives_hold(scr, A, B, st)
+    print("n3 with", OTHER_CC, "from", WALL_CLOCK_US, {k: st[k] for k in ("rounds", "fired", "retx_delivered", "late")},
+          "cutbacks", sum(k.cutbacks for E in (A, B) for k in E.cc), "rtos", sum(k.rtos for E in (A, B) for k in E.cc))
+    assert st["fired"] > 0 and all(k.p == dict(OTHER_CC) for k in A.cc) and max(k.cwnd for k in A.cc + B.cc) <= 60
 
 
 # ---------------------------------------------------------------- GPU
@@ -98,7 +108,7 @@ def enc(gpu):
     return fec.New(10, 3)
 
 
-def run_on_device(enc, name, where="device"):
+def run_on_device(enc, name, where="device", **more):
     made = []
 
     def make(n, now, **kw):
@@ -106,7 +116,7 @@ def run_on_device(enc, name, where="device"):
         return made[-1]
 
     try:
-        scr, A, B, st = run(name, make)
+        scr, A, B, st = run(name, make, **more)
         lives_hold(scr, A, B, st)
         return st
     finally:
@@ -121,6 +131,14 @@ def test_chain_equals_the_rules_call_by_call(enc, n):
     a block, and one wave holds live, closing, lingering, failing and exited
     lanes together."""
     run_on_device(enc, f"n{n}")
+
+
+@pytest.mark.gpu
+def test_chain_with_other_congestion_parameters_from_a_wall_clock(enc):
+    """The controllers of both endpoints at (10, 60, 3, 1, 1000), every clock
+    above 2^50 us."""
+    st = run_on_device(enc, "n3", start_us=WALL_CLOCK_US, cc_params=OTHER_CC)
+    assert st["fired"] > 0
 
 
 @pytest.mark.gpu

@@ -50,6 +50,26 @@ SHORT_FLOORS = dict(FLOORS, lapped=0, lapped_once=1)
 RX_FLOORS = dict(rx_truncated=1, rx_old=500, rx_mixed_stretches=100, rx_attached=100)
 
 
+# The same families from real clocks, 8 rounds each (the floors above are for 20 rounds and do not apply).
+# T1 starts 6,750 or 8,750 us below 2^32 us (71.6 minutes of uptime), so that the boundary falls between the record
+# and the ack of the round whose RTO step follows: the third round of the sent family, the fourth of the others.
+# T2 is a wall clock in us, T3 is no double, T4 ends 10^8 us short of 2^64 (a clock of 0 means unset, and no call
+# may pass 2^64).
+CLOCK_ROUNDS = 8
+T2, T3, T4 = 1_760_000_000_000_000, (1 << 53) + 1, (1 << 64) - 10 ** 8
+CLOCK_SENT, CLOCK_CC, CLOCK_ACK = (2, 4), 7, (6, 4)
+T1_SENT, T1_CC, T1_ACK = hf.EDGE - 6750, hf.EDGE - 8750, hf.EDGE - 8750
+SENT_BASES = [T1_SENT, T2, T3, T4]
+CC_BASES = [T1_CC, T2, T3, T4]
+ACK_BASES = [T1_ACK, T2, T3]
+
+
+def _clock_family(kind, start_us):
+    if kind == "cc":
+        return hf.Family(CLOCK_CC, CC_MAX_RANGES, rounds=CLOCK_ROUNDS, start_us=start_us)
+    return hf.Family(*(CLOCK_SENT if kind == "sent" else CLOCK_ACK), rounds=CLOCK_ROUNDS, start_us=start_us)
+
+
 def _hold(fam, st, floors):
     print(fam, {k: st[k] for k in floors}, "inert", st["inert"], "inert peers", st["inert_peers"])
     for k, v in floors.items():
@@ -81,6 +101,34 @@ def test_the_families_reach_what_they_are_for():
     _hold(fam, st, SHORT_FLOORS)
     inert += st["inert"]
     assert inert >= 1, "no sent family on the device keeps an inert member beside live ones"
+
+
+def test_the_families_at_real_clocks_reach_what_they_are_for():
+    """The rules alone through every (family, base) of the GPU tests: no run is
+    idle, and the runs from T1 carry an RTT sample, an RTO and a lo_time_us
+    across 2^32 us."""
+    for kind, bases in (("sent", SENT_BASES), ("cc", CC_BASES), ("ack", ACK_BASES)):
+        for base in bases:
+            fam = _clock_family(kind, base)
+            ops = hf.RuleCcOps(fam) if kind == "cc" else hf.RuleOps(fam)
+            st = hf.run(fam, ops, hf.RuleRx(fam) if kind == "ack" else None)
+            keys = ("first_clock", "last_clock", "rtos", "cutbacks", "clamped_drains", "queued_present", "rtt_across",
+                    "rto_across", "lo_time_across", "rx_attached", "inert", "inert_peers", "rx_inert")
+            print(kind, fam, {k: st[k] for k in keys})
+            assert base == st["first_clock"] < st["last_clock"] < 1 << 64
+            assert st["rtos"] >= 1 and st["clamped_drains"] + st["queued_present"] >= 1, dict(st)
+            assert kind != "cc" or st["cutbacks"] >= 1, dict(st)
+            quarter = fam.nconn // 4
+            assert st["inert"] <= quarter and st["inert_peers"] <= quarter and st["rx_inert"] <= quarter, dict(st)
+            if base in (T1_SENT, T1_CC, T1_ACK):
+                assert st["first_clock"] < hf.EDGE < st["last_clock"]
+                if kind == "ack":                          # its sending side is the rules alone, only a source
+                    assert st["lo_time_across"] >= 1 and st["rx_attached"] >= 1, dict(st)
+                else:
+                    assert st["rtt_across"] >= 1 and st["rto_across"] >= 1, dict(st)
+            else:
+                assert st["rtt_across"] == st["rto_across"] == st["lo_time_across"] == 0
+                assert (st["first_clock"] < hf.EDGE) == (st["last_clock"] < hf.EDGE)
 
 
 def test_a_failing_call_is_named_and_can_be_replayed_without_a_gpu():
@@ -169,5 +217,42 @@ def test_sent_family_on_pinned_operands(enc):
     h = SentHarness(enc, fam.wss, fam.seg_cap)
     try:
         hf.run(fam, hf.DeviceOps(h, where="pinned"))
+    finally:
+        h.close()
+
+
+def _base_id(base):
+    return "T1" if base < 1 << 33 else "T2" if base == T2 else "T3" if base == T3 else "T4"
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("base", SENT_BASES, ids=_base_id)
+def test_sent_family_at_real_clocks(enc, base):
+    fam = _clock_family("sent", base)
+    h = SentHarness(enc, fam.wss, fam.seg_cap)
+    try:
+        hf.run(fam, hf.DeviceOps(h))
+    finally:
+        h.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("base", CC_BASES, ids=_base_id)
+def test_cc_family_at_real_clocks(enc, base):
+    fam = _clock_family("cc", base)
+    ch = CcHarness(enc, fam.wss, fam.seg_cap)
+    try:
+        hf.run(fam, hf.DeviceCcOps(ch, fam.max_ranges))
+    finally:
+        ch.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("base", ACK_BASES, ids=_base_id)
+def test_ack_family_at_real_clocks(enc, base):
+    fam = _clock_family("ack", base)
+    h = AckHarness(enc, fam.wss)
+    try:
+        hf.run(fam, hf.RuleOps(fam), hf.DeviceRx(h))
     finally:
         h.close()

@@ -547,21 +547,26 @@ def test_receive_a_thousand_ending_packets_among_a_hundred_thousand_of_one_membe
     h.close()
 
 
-def _inject(h, nconn):
-    """Errors and progress in the neighbouring sets, through their own calls.
-    Returns the members touched, by what."""
+def _inject_members(nconn):
     if nconn < 16:                                                        # the errors share members 0 and 1
-        m = dict(sent_err=0, ack_err=1, stream_err=1, failures=2, tracked=2, unsent=2)
-    else:
-        m = {k: 3 + 5 * j for j, k in enumerate(("sent_err", "ack_err", "stream_err", "failures", "tracked",
-                                                 "unsent"))}
-    h.sent_record([(m["sent_err"], 1), (m["tracked"], 20)] + [(m["failures"], k) for k in range(1, 14)], 1000)
-    h.sent_record([(m["sent_err"], 5000)], 1001)                          # past the window: TOO_MANY_TRACKED
-    now = 1000
+        return dict(sent_err=0, ack_err=1, stream_err=1, failures=2, tracked=2, unsent=2)
+    return {k: 3 + 5 * j for j, k in enumerate(("sent_err", "ack_err", "stream_err", "failures", "tracked", "unsent"))}
+
+
+def _inject(h, nconn, base=0):
+    """Errors and progress in the neighbouring sets, through their own calls.
+    Returns the members touched, by what.  The eleven RTOs take 671 s, which
+    do not fit between the highest base and 2^64: above base 0 the neighbours'
+    clocks start 700 s below base and so end below it."""
+    m = _inject_members(nconn)
+    at = base - 700_000_000 if base else 0
+    h.sent_record([(m["sent_err"], 1), (m["tracked"], 20)] + [(m["failures"], k) for k in range(1, 14)], at + 1000)
+    h.sent_record([(m["sent_err"], 5000)], at + 1001)                     # past the window: TOO_MANY_TRACKED
+    now = at + 1000
     for _ in range(11):                                                   # eleven RTOs in a row
         now += 61_000_000
         h.sent_rto(now)
-    h.ack_receive([(m["ack_err"], 2 * k + 2) for k in range(1001)], 5)    # 1,001 outstanding
+    h.ack_receive([(m["ack_err"], 2 * k + 2) for k in range(1001)], at + 5)    # 1,001 outstanding
     h.stream_deliver([(m["stream_err"], 10, 10)])
     h.stream_deliver([(m["stream_err"], 5, 10)])                          # overlaps
     counts = [0] * nconn
@@ -574,21 +579,30 @@ def _inject(h, nconn):
     return m
 
 
-@pytest.mark.gpu
-@pytest.mark.parametrize("nconn", [3, 1025, 32769])
-def test_the_loop_equals_the_rule_in_every_mode_at_once(enc, nconn):
-    """Six batches through receive, close, check, append and sent.  Every member
-    draws its own packets, closes and clocks, so the lanes of one wave are live,
-    closing, lingering, failing and exited at once; the clocks step by the
-    boundaries of the delayed ACK, the linger and the idle tests."""
+class _DryLoop:
+    """Takes the calls of _every_mode and does nothing: what the script draws
+    does not depend on what the device answers, so its clocks can be had
+    without one."""
+    rules = ()
+
+    def __getattr__(self, name):
+        return lambda *a, **k: (0, [], [], 0, [], 0)
+
+
+EVERY_MODE_IDLE = 40_000
+
+
+def _every_mode(h, nconn, base, who):
+    """The body of test_the_loop_equals_the_rule_in_every_mode_at_once, every
+    clock above base.  Returns the clocks of the loop calls."""
     rng = np.random.default_rng(nconn)
-    idle = 40_000
-    h = LoopHarness(enc, nconn, now_us=1000, idle_us=idle, ack_delay_us=5000)
-    who = _inject(h, nconn)
-    now = 1000
+    idle = EVERY_MODE_IDLE
+    now = base + 1000
     seen = set()
+    clocks = []
     for rnd in range(6):
         now += int(rng.choice([0, 1, 4999, 5000, 5001, 7000, idle - 5001]))
+        clocks.append(now)
         npk = int(rng.integers(4096, 20001))
         conn = rng.integers(0, nconn, npk).astype(np.uint32)
         conn[rng.random(npk) < 0.02] = NO_CONN
@@ -609,6 +623,7 @@ def test_the_loop_equals_the_rule_in_every_mode_at_once(enc, nconn):
             how[[who["tracked"], who["unsent"]]], linger[[who["tracked"], who["unsent"]]] = 1, (1, 5001)
         h.close_members(how, now, None if rnd == 0 else linger)
         now += int(rng.choice([0, 1, 5000, 5001]))
+        clocks.append(now)
         budget = rng.integers(0, 9, nconn)
         h.check_call(now, budget)
         total = int(rng.integers(0, 50))
@@ -619,13 +634,55 @@ def test_the_loop_equals_the_rule_in_every_mode_at_once(enc, nconn):
         out = h.sent(rng.integers(0, 2, nconn), rng.integers(0, 2, nconn), now, None if rnd == 2 else delay,
                      max_exits=int(rng.choice([0, 1, 7, nconn])), remap=rnd != 3)
         seen |= set(out[2])
+    return clocks
+
+
+def _loop_in_every_mode(enc, nconn, base):
+    h = LoopHarness(enc, nconn, now_us=base + 1000, idle_us=EVERY_MODE_IDLE, ack_delay_us=5000)
+    who = _inject(h, nconn, base)
+    clocks = _every_mode(h, nconn, base, who)
     reasons = {r.reason for r in h.rules}
     if nconn >= 1025:
         assert reasons >= set(range(1, 12)), sorted(reasons)
         assert {who[k] for k in who} and all(h.rules[who[k]].exited for k in ("sent_err", "ack_err", "stream_err",
                                                                              "failures"))
         assert any(r.fin_sent for r in h.rules) and any(r.dropped for r in h.rules)
+    rules = h.rules
     h.close()
+    return clocks, rules
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("nconn", [3, 1025, 32769])
+def test_the_loop_equals_the_rule_in_every_mode_at_once(enc, nconn):
+    """Six batches through receive, close, check, append and sent.  Every member
+    draws its own packets, closes and clocks, so the lanes of one wave are live,
+    closing, lingering, failing and exited at once; the clocks step by the
+    boundaries of the delayed ACK, the linger and the idle tests."""
+    _loop_in_every_mode(enc, nconn, 0)
+
+
+# Real clocks.  T1 is placed by the script's own clocks (had without a device) so that the fourth batch is the
+# first at or past 2^32 us; T2 is a wall clock in us; T4 ends 10^8 us short of 2^64.
+_DRY_CLOCKS = _every_mode(_DryLoop(), 1025, 0, _inject_members(1025))
+T1 = (1 << 32) - _DRY_CLOCKS[6]
+T2, T4 = 1_760_000_000_000_000, (1 << 64) - 10 ** 8
+BASE_IDS = {T1: "T1", T2: "T2", T4: "T4"}
+
+
+def test_the_clocks_of_the_every_mode_script_cross_2_32_in_mid_run():
+    clocks = _every_mode(_DryLoop(), 1025, T1, _inject_members(1025))
+    print("loop clocks from T1, less 2^32:", [t - (1 << 32) for t in clocks])
+    assert len(clocks) == 12 and clocks == sorted(clocks)
+    assert clocks[0] < clocks[5] < 1 << 32 == clocks[6] and clocks[-1] > clocks[6]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("base", [T1, T2, T4], ids=BASE_IDS.get)
+def test_the_loop_equals_the_rule_in_every_mode_at_once_at_real_clocks(enc, base):
+    clocks, rules = _loop_in_every_mode(enc, 1025, base)
+    assert base < clocks[0] and clocks[-1] < 1 << 64 and clocks == [base + t for t in _DRY_CLOCKS]
+    assert all(r.exited or r.origin_ack_us == 0 or r.origin_ack_us > base for r in rules)
 
 
 def _pad(slot):
@@ -686,28 +743,52 @@ def test_appended_records_encode_as_the_references_fin_and_rst(enc):
     h.close()
 
 
+def _deadline_terms(enc, base):
+    """Each term of the deadline the minimum in turn, every clock above base.
+    Returns the deadlines less base, in the order asked, and the last output."""
+    idle = 10 ** 9
+    h = LoopHarness(enc, 4, now_us=base + 1000, idle_us=idle)
+    none = [0] * 4
+    got = [h.sent(none, none, base + 1000)[0]]                            # the idle term
+    st, fl, pn, conn = _batch(1, 1)
+    h.receive(st, fl, pn, conn, base + 2000)
+    got.append(h.sent(none, none, base + 2000)[0])                        # the delayed ACK
+    h.sent_record([(2, 1), (3, 1)], base + 1)                             # last_sent_us = 1: an RTO at 500,001
+    h.close_members([0, 0, 1, 0], base + 2500, [0, 0, 3000, 0])
+    got.append(h.sent(none, none, base + 2500)[0])                        # the linger deadline
+    got.append(h.sent([0, 1, 0, 0], none, base + 2600)[0])
+    assert h.rules[1].origin_ack_us == 0
+    h.check_call(base + 5500, none)
+    assert h.rules[2].reason == lf.LINGER
+    got.append(h.sent(none, none, base + 5500)[0])                        # the RTO, default delay
+    got.append(h.sent(none, none, base + 5500, delay_us=[0, 0, 0, 300_000])[0])
+    got.append(h.sent(none, none, base + 300_001, delay_us=[0, 0, 0, 300_000])[0])            # not after now
+    h.close_members([2] * 4, base + 6000)
+    out = h.sent(none, none, base + 6000, remap=True)
+    h.close()
+    return [lf.NEVER if t == lf.NEVER else t - base for t in got], out
+
+
 @pytest.mark.gpu
 def test_sent_deadline_each_term_the_minimum_in_turn(enc):
     idle = 10 ** 9
-    h = LoopHarness(enc, 4, now_us=1000, idle_us=idle)
-    none = [0] * 4
-    assert h.sent(none, none, 1000)[0] == 1000 + idle                     # the idle term
-    st, fl, pn, conn = _batch(1, 1)
-    h.receive(st, fl, pn, conn, 2000)
-    assert h.sent(none, none, 2000)[0] == 2000 + 5000                     # the delayed ACK
-    h.sent_record([(2, 1), (3, 1)], 1)                                    # last_sent_us = 1: an RTO at 500,001
-    h.close_members([0, 0, 1, 0], 2500, [0, 0, 3000, 0])
-    assert h.sent(none, none, 2500)[0] == 5500                            # the linger deadline
-    assert h.sent([0, 1, 0, 0], none, 2600)[0] == 5500 and h.rules[1].origin_ack_us == 0
-    h.check_call(5500, none)
-    assert h.rules[2].reason == lf.LINGER
-    assert h.sent(none, none, 5500)[0] == 500_001                         # the RTO, default delay
-    assert h.sent(none, none, 5500, delay_us=[0, 0, 0, 300_000])[0] == 300_001
-    assert h.sent(none, none, 300_001, delay_us=[0, 0, 0, 300_000])[0] == min(1000, 2000) + idle  # not after now
-    h.close_members([2] * 4, 6000)
-    out = h.sent(none, none, 6000, remap=True)
+    got, out = _deadline_terms(enc, 0)
+    assert got == [1000 + idle, 2000 + 5000, 5500, 5500, 500_001, 300_001, min(1000, 2000) + idle]
     assert out[0] == lf.NEVER and out[4] == [NO_CONN] * 4 and out[5] == 0  # no live member
-    h.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("base", [T1, T2, T4], ids=BASE_IDS.get)
+def test_sent_deadline_each_term_the_minimum_in_turn_at_real_clocks(enc, base):
+    """The harness holds every deadline to the rule's; what the rule gives is
+    the same terms above base, but that at T4 the idle term, 10^9 us ahead,
+    passes 2^64 and saturates to NEVER."""
+    idle = 10 ** 9
+    got, out = _deadline_terms(enc, base)
+    far = lf.NEVER if base == T4 else None
+    assert base + 1000 + idle >= 1 << 64 if base == T4 else base + 2000 + idle < 1 << 64
+    assert got == [far or 1000 + idle, 2000 + 5000, 5500, 5500, 500_001, 300_001, far or min(1000, 2000) + idle]
+    assert out[0] == lf.NEVER and out[4] == [NO_CONN] * 4 and out[5] == 0
 
 
 @pytest.mark.gpu

@@ -558,6 +558,25 @@ def test_rto_deadline_backoff_and_cap(enc):
 
 
 @pytest.mark.gpu
+def test_a_deadline_past_2_64_never_comes(enc):
+    """The RTO is at most 60 s, so last_sent_us + rto passes 2^64 only in the
+    last minute of the clock: member 0 sent 30 s before 2^64, member 1 70 s
+    before it, both wait the capped 60 s.  At the last clock there is, member
+    1's deadline has passed and member 0's never comes; a sum that wrapped
+    would have it due since long."""
+    top = 1 << 64
+    h = SentHarness(enc, [1024] * 2, 1)
+    h.send(1, range(1, 5), now_us=top - 70_000_000)
+    h.send(0, range(1, 5), now_us=top - 30_000_000)
+    assert h.rto([60_000_000] * 2, top - 10_000_001) == [0, 0]
+    assert h.rto([60_000_000] * 2, top - 10_000_000) == [0, 1]                      # at member 1's deadline
+    assert h.rto([60_000_000] * 2, top - 1) == [0, 0]                               # member 1 backs off: 60 s again
+    assert h.rto([10 ** 9, 200_000], top - 1) == [0, 1]                             # 400 ms: due; 0 is capped at 60 s
+    assert h.rto([0, 0], top - 1) == [1, 0]                                         # 500 ms: due since 29.5 s; 1's 2 s wrap
+    h.close()
+
+
+@pytest.mark.gpu
 def test_drain_order_tail_clamp_touch_and_upto(enc):
     h = SentHarness(enc, [1024] * 3, 2)
     h.record([(c, n, 100, 0, 0x80 if (c, n) == (1, 3) else 0, 5 if (c, n) == (0, 1) else 0,
